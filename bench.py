@@ -1,6 +1,6 @@
 """North-star benchmark: 3 s-clip train steps/s (B=32 per GPU, xattn fusion) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,12 @@ WavLM runs with the reference's train-mode semantics (the reference keeps the fr
 under no_grad, train.py:194): SpecAugment, dropout and LayerDrop -- so the algorithmic FLOPs of a step count
 only the encoder layers actually executed; `wavlm_layers_per_step` reports them.
 
-Extra fields: `roofline` for the dominant kernel (after the timed region: HIP events around `--probe-launches`
+A plain run sets up, warms up, times the K steps, writes its outputs when ``--dump-outputs DIR`` is given
+(`dump_outputs`: what the last timed step returned and left behind, as DIR/<name>.npy; the inputs and the initial
+weights are seeded, so two builds run with the same arguments can be compared output for output) and prints the
+result line.  Everything below takes runs of its own and is measured only with ``--full``.
+
+Extra fields (``--full``): `roofline` for the dominant kernel (after the timed region: HIP events around `--probe-launches`
 standalone launches of that kernel on its production shape, weights and stream, with nothing else in flight --
 the figure a rocprofv3 kernel trace of the same command reports for it; the timed schedule is never altered),
 `roofline_head` for the fused xattn head (HIP events around its graph replays in `--probe-steps` steps) and
@@ -129,6 +134,44 @@ def synthetic_batch(device, seed):
     audio = (0.1 * torch.randn(BATCH, 1, SAMPLES, device=device, generator=g)).clamp_(-1, 1)
     labels = torch.randint(0, CLASSES, (BATCH,), device=device, generator=g)
     return video.contiguous(), audio.contiguous(), labels
+
+
+DUMP_SAMPLE = 1 << 18  # elements kept of a larger array (a fixed, seeded sample): the whole dump stays well below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs DIR``: write ``arrays`` ({name: tensor}) as DIR/<name>.npy, float32 (float64 for float64 and
+    integer tensors).  An array of more than DUMP_SAMPLE elements is written as the sample at seeded, sorted flat
+    indices that depend on its name's position and its size alone, so two builds write the same elements."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for i, (name, t) in enumerate(arrays.items()):
+        t = t.detach()
+        t = t.to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64)
+        a = t.cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(1000 + i).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        assert total <= 64 << 20, "dump_outputs: more than 64 MB"
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a))
+
+
+def step_outputs(model, loss, preds):
+    """What a caller of one ``TrainStep`` receives: the returned loss and top-1 predictions, and the state the step
+    left in the model -- every trainable parameter after Adam and the floating-point buffers (BatchNorm running
+    statistics).  Frozen parameters are unchanged by the step and are left out."""
+    arrays = {"loss": loss.reshape(1), "preds": preds}
+    for n, p in model.named_parameters():
+        if p.requires_grad:
+            arrays["param." + n] = p
+    for n, b in model.named_buffers():
+        if b.is_floating_point():
+            arrays["buffer." + n] = b
+    return arrays
 
 
 def box_peaks():
@@ -347,11 +390,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the rooflines (probe steps and launches, box peaks) and "
+                         "the CPU baseline; a plain run times its steps and prints the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--probe-steps", type=int, default=10,
-                    help="instrumented steps after the timed region in which the fused head's graphs are timed")
+                    help="(--full) instrumented steps after the timed region in which the fused head's graphs are timed")
     ap.add_argument("--probe-launches", type=int, default=20,
-                    help="standalone launches of the dominant kernel timed after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="(--full) standalone launches of the dominant kernel timed after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: this process's CPU share (cpu_share_threads)")
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=10)
@@ -372,6 +420,11 @@ def main():
     ap.add_argument("--stub-step", action="store_true",
                     help="test hook for the rank launcher: a CPU matmul + gloo all-reduce in place of the train step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # the plain run: nothing but the timed steps
+        args.probe_steps = args.probe_launches = 0
+        args.no_cpu_baseline = True
 
     world, rank, local = init_distributed("gloo" if args.stub_step else None)
     if world != args.gpus:
@@ -554,8 +607,10 @@ def _bench_c5(args, world, rank, local):
                    "per_gpu_batch": B, "parallelism": f"replicas{world}"},
         "bf16": res["bf16"], "int8": res["int8"], "top1_agreement_int8_vs_bf16": agree,
         "max_abs_prob_diff_int8_vs_bf16": round(float((probs["int8"] - probs["bf16"]).abs().max()), 6),
-        "peaks": box_peaks(), "cpu_baseline": None,
+        "peaks": box_peaks() if args.full else None, "cpu_baseline": None,
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"probs_" + k: v for k, v in probs.items()})
     if world == 1 and not args.no_cpu_baseline:
         threads = args.cpu_threads if args.cpu_threads > 0 else cpu_share_threads()
         out["cpu_baseline"] = cpu_baseline_c5(threads)
@@ -596,10 +651,11 @@ def _bench(args, world, rank, local):
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
     marks[0].record()
-    loss = None
+    loss = last = None
     for i in range(args.steps):
-        loss, _ = step(video, audio, labels, next_audio=nxt)
+        last = step(video, audio, labels, next_audio=nxt)
         marks[i + 1].record()
+    loss = last[0]
     torch.cuda.synchronize()
     local_ms = (time.perf_counter() - t0) / args.steps * 1e3  # this rank alone, before the closing barrier
     if is_dist():
@@ -610,6 +666,8 @@ def _bench(args, world, rank, local):
                                                                            step_ms[len(step_ms) // 2])
     layers = (wav.executed_layers - lay0) / max(1, wav.train_forwards - fwd0)
     dp = dp_fields(local_ms, sync, dev) if is_dist() else None
+    if args.dump_outputs and rank == 0:  # before any probe step runs the optimizer again
+        dump_outputs(args.dump_outputs, step_outputs(model, *last))
 
     # probe steps (after the timed region): the fused head's forward / backward graph replays bracketed by HIP
     # events on their stream
@@ -625,8 +683,8 @@ def _bench(args, world, rank, local):
     if args.probe_launches > 0:
         time_dominant(model, dev, probe, args.probe_launches)
     kms = probe.avg_ms()
-    peaks = box_peaks()
-    peak_bf16 = peaks["bf16_dense_tflops"]
+    peaks = box_peaks() if args.full else None  # (asks rocminfo: a child process)
+    peak_bf16 = peaks["bf16_dense_tflops"] if peaks else PEAK_BF16_TFLOPS
     peak_split = peak_bf16 / 3
     roof = None
     if kms:
