@@ -455,6 +455,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
   constexpr int BUF = KS * (BM_ + BN_);                 // bf16 elements per ring slot
   extern __shared__ __attribute__((aligned(16))) bf16_t smem_all[];
   const int t = threadIdx.x, lane = t & 63, kg = (t >> 6) / WAVES, w = (t >> 6) % WAVES;
+  CTP(0);  // (timing build: tools/pipe_phases.py, slots as in conv_pipe_kernel)
   bf16_t* const smem = smem_all + kg * STAGES * BUF;  // this K-group's ring
   const int Ntot = g.R * g.S * g.C;
   const int P = g.N * g.Ho * g.Wo;
@@ -479,51 +480,81 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
   const int wm = (w / WN) * (BM_ / WM), wn = (w % WN) * (BN_ / WN);
   const bf16_t* zero = reinterpret_cast<const bf16_t*>(mer_conv_zero16);
 
-  // per-lane constants of each glds: its LDS row inside the K-step and its (logical) column chunk
-  int arow[IA], acol[IA];
+  // this K-group's K-steps [kb, kb + nk) of the split's nk_all (every group runs the loop nkg times: workgroup-wide
+  // barriers)
+  const int nk_all = (p_end - p_beg + KS - 1) / KS;
+  const int nkg = (nk_all + KG - 1) / KG, kb = __builtin_amdgcn_readfirstlane(kg * nkg);  // (kg is wave-uniform)
+  const int nk = nk_all - kb < nkg ? (nk_all - kb > 0 ? nk_all - kb : 0) : nkg;
+  const int pk0 = p_beg + kb * KS;
+
+  // Staging walks the pixels incrementally: K-steps are staged strictly in order, pk0 first, and a lane's pixel moves
+  // KS pixels per step.  Per DMA a lane keeps its source pointer (it may lie outside the tensor -- padding taps, pixels
+  // past the split -- and is then only ever an operand of a select against the zero chunk) and, for the X operand, the
+  // output pixel's (oh, ow): KS = (dn, dh, dw) in (image, row, column) steps is split once, so a step is two bounded
+  // carries and one pointer add -- no division and no 64-bit multiply in the loop.
+  const int HoWo = g.Ho * g.Wo;
+  const bf16_t* ap[IA];  // dY: linear in the pixel
+  int arow[IA];
   bool acok[IA];
 #pragma unroll
   for (int j = 0; j < IA; ++j) {
-    const int row = (w * IA + j) * ARI + lane / ACW;
-    arow[j] = row;
-    acol[j] = m0 + ((lane % ACW) ^ wswz(row, ACW)) * 8;
-    acok[j] = acol[j] < g.K;
+    arow[j] = (w * IA + j) * ARI + lane / ACW;
+    const int acol = m0 + ((lane % ACW) ^ wswz(arow[j], ACW)) * 8;
+    acok[j] = acol < g.K;
+    ap[j] = g.dY + ((long)(pk0 + arow[j]) * g.ldy + acol);
   }
-  int brow[IB], bc[IB], br[IB], bs[IB];
+  const long a_step = (long)KS * g.ldy;
+  const bf16_t* bp[IB];  // X: the tap's pixel of output pixel (n, oh, ow), channel chunk included
+  int brow[IB], boh[IB], bow[IB], bdr[IB], bds[IB];  // tap offset (dr, ds) = (r - pad, s - pad)
   bool bcok[IB];
-  const float inv_C = 1.f / g.C, inv_S = 1.f / g.S, inv_HoWo = 1.f / (g.Ho * g.Wo), inv_Wo = 1.f / g.Wo;
 #pragma unroll
   for (int j = 0; j < IB; ++j) {
-    const int row = (w * IB + j) * BRI + lane / BCW;
-    brow[j] = row;
-    const int col = n0 + ((lane % BCW) ^ wswz(row, BCW)) * 8;
+    brow[j] = (w * IB + j) * BRI + lane / BCW;
+    const int col = n0 + ((lane % BCW) ^ wswz(brow[j], BCW)) * 8;
     bcok[j] = col < Ntot;
     const int cc = bcok[j] ? col : 0;
-    const int tap = fdiv(cc, inv_C);
-    bc[j] = cc - tap * g.C;
-    br[j] = fdiv(tap, inv_S);
-    bs[j] = tap - br[j] * g.S;
+    const int tap = cc / g.C, c = cc - tap * g.C;
+    const int r = tap / g.S;
+    bdr[j] = r - g.pad;
+    bds[j] = tap - r * g.S - g.pad;
+    const int p = pk0 + brow[j];
+    const int n = p / HoWo, rem = p - n * HoWo;
+    boh[j] = rem / g.Wo;
+    bow[j] = rem - boh[j] * g.Wo;
+    bp[j] = g.X + ((((long)n * g.H + boh[j] * g.st + bdr[j]) * g.W + bow[j] * g.st + bds[j]) * g.C + c);
   }
-  const int HoWo = g.Ho * g.Wo;
-  auto stage = [&](int slot, int p0) {
+  const int s_dn = KS / HoWo, s_rem = KS - s_dn * HoWo, s_dh = s_rem / g.Wo, s_dw = s_rem - s_dh * g.Wo;
+  const int d_step = ((s_dn * g.H + s_dh * g.st) * g.W + s_dw * g.st) * g.C;  // element deltas: the plain step,
+  const int d_wrap_w = g.st * (g.W - g.Wo) * g.C;                            // ow -= Wo, oh += 1
+  const int d_wrap_h = (g.H - g.Ho * g.st) * g.W * g.C;                      // oh -= Ho, n += 1
+  int p_left = p_end - pk0;  // pixels of the split from the K-step being staged on
+  auto stage = [&](int slot) {
     bf16_t* la = smem + slot * BUF;
     bf16_t* lb = la + KS * BM_;
 #pragma unroll
     for (int j = 0; j < IA; ++j) {
-      const int p = p0 + arow[j];
-      glds16(p < p_end && acok[j] ? g.dY + (long)p * g.ldy + acol[j] : zero, la + (w * IA + j) * 512);
+      glds16(((int)(arow[j] < p_left) & (int)acok[j]) ? ap[j] : zero, la + (w * IA + j) * 512);
+      ap[j] += a_step;
     }
 #pragma unroll
     for (int j = 0; j < IB; ++j) {
-      const int p = p0 + brow[j];
-      const int pc = p < p_end ? p : p_beg;
-      const int n = fdiv(pc, inv_HoWo);
-      const int rem = pc - n * HoWo;
-      const int oh = fdiv(rem, inv_Wo), ow = rem - oh * g.Wo;
-      const int ih = oh * g.st - g.pad + br[j], iw = ow * g.st - g.pad + bs[j];
-      const bool ok = p < p_end && bcok[j] && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
-      glds16(ok ? g.X + (((long)n * g.H + ih) * g.W + iw) * g.C + bc[j] : zero, lb + (w * IB + j) * 512);
+      // (all four tests evaluated, one select: no per-lane branch)
+      const int ok = (int)(brow[j] < p_left) & (int)bcok[j] &
+                     (int)((unsigned)(__mul24(boh[j], g.st) + bdr[j]) < (unsigned)g.H) &
+                     (int)((unsigned)(__mul24(bow[j], g.st) + bds[j]) < (unsigned)g.W);
+      glds16(ok ? bp[j] : zero, lb + (w * IB + j) * 512);
+      int d = d_step;
+      bow[j] += s_dw;
+      const bool cw = bow[j] >= g.Wo;
+      bow[j] -= cw ? g.Wo : 0;
+      d += cw ? d_wrap_w : 0;
+      boh[j] += s_dh + (cw ? 1 : 0);
+      const bool ch = boh[j] >= g.Ho;
+      boh[j] -= ch ? g.Ho : 0;
+      d += ch ? d_wrap_h : 0;
+      bp[j] += d;
     }
+    p_left -= KS;
   };
   // transposed fragment from a swizzled image with CW chunks per row: elements j = 0..7 =
   // Img[k0 + 8*(lane>>4) + j][c0 + (lane&15)]
@@ -547,24 +578,22 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
   for (int i = 0; i < IT; ++i)
 #pragma unroll
     for (int j = 0; j < JT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // this K-group's K-steps [kb, kb + nk) of the split's nk_all (every group runs the loop nkg times: workgroup-wide
-  // barriers)
-  const int nk_all = (p_end - p_beg + KS - 1) / KS;
-  const int nkg = (nk_all + KG - 1) / KG, kb = kg * nkg;
-  const int nk = nk_all - kb < nkg ? (nk_all - kb > 0 ? nk_all - kb : 0) : nkg;
-  const int pk0 = p_beg + kb * KS;
   constexpr int G = IA + IB;
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s)
-    if (s < nk) stage(s, pk0 + s * KS);
+    if (s < nk) stage(s);
+  int wslot = STAGES - 1, rslot = 0;  // ring slots: wrapping counters
+  CTP(1);
   for (int kt = 0; kt < nkg; ++kt) {
     const int left = nk - 1 - kt;
     const int ahead = left < (STAGES - 2) ? left : (STAGES - 2);
     wait_tiles_in_flight<G>(ahead);
     lds_barrier();
-    if (kt + STAGES - 1 < nk) stage((kt + STAGES - 1) % STAGES, pk0 + (kt + STAGES - 1) * KS);
+    if (kt + STAGES - 1 < nk) stage(wslot);
+    wslot = wslot == STAGES - 1 ? 0 : wslot + 1;
+    const bf16_t* Aimg = smem + rslot * BUF;
+    rslot = rslot == STAGES - 1 ? 0 : rslot + 1;
     if (KG > 1 && kt >= nk) continue;
-    const bf16_t* Aimg = smem + (kt % STAGES) * BUF;
     const bf16_t* Bimg = Aimg + KS * BM_;
 #pragma unroll
     for (int s = 0; s < KS / 32; ++s) {
@@ -581,6 +610,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
       __builtin_amdgcn_s_setprio(0);
     }
   }
+  CTP(2);
   if constexpr (KG > 1) {  // groups 1.. hand their tiles to group 0 through LDS; group 0 sums in group order
     constexpr int LDR = BN_ + 4;
     __syncthreads();  // every group's last fragment reads are done before the exchange reuses the rings
@@ -608,6 +638,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
             acc[i][j][rr] += part[(q - 1) * BM_ * LDR + (wm + i * 16 + (lane >> 4) * 4 + rr) * LDR + wn + j * 16 +
                                   (lane & 15)];
   }
+  CTP(3);
   float* slab = g.ws + (long)zs * g.K * Ntot;
 #pragma unroll
   for (int i = 0; i < IT; ++i)
@@ -621,6 +652,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
         if (k < g.K) slab[(long)k * Ntot + nn] = acc[i][j][rr];
       }
     }
+  CTP(4);
 }
 
 template <int BM_, int BN_, int WM, int WN, int STAGES, int KS = 64, int KG = 1>
@@ -1363,8 +1395,11 @@ struct KgLayout {
 // through the same barriers; at the end every group stores its fp32 tile to LDS and the WAVES * KG waves re-split the
 // tile (KgLayout), each element summed over the groups in group order -- deterministic, no global partials, and the
 // fused epilogue (BN statistics / BN-backward sums) runs unchanged on the summed tile.
+//
+// FAST: the scalar-walk staging (see there), picked by the launcher (`fast` in launch_conv_pipe_t) where the shape
+// allows it.
 template <bool DGRAD, bool PAR, int BM_, int BN_, int WM = 2, int WN = 2, int STAGES = 2, int KS = 64, bool X2 = true,
-          int KG = 1>
+          int KG = 1, bool FAST = false>
 // (__launch_bounds__'s second argument is amdgpu_waves_per_eu, a minimum of waves per SIMD: two 8-wave blocks per CU need
 // 4, i.e. <= 128 VGPRs -- with 2, the parity-class dgrad tile took 131 VGPRs and ran one block per CU)
 __global__ __launch_bounds__(64 * WM * WN * KG, conv_pipe_wpe(WM * WN * KG, BM_, BN_, STAGES, DGRAD, PAR,
@@ -1404,68 +1439,30 @@ __global__ __launch_bounds__(64 * WM * WN * KG, conv_pipe_wpe(WM * WN * KG, BM_,
   const int m0 = ty * BM_, n0 = tx * BN_;
   const int wr = w / WN, wc = w % WN;
 
-  int an[IA], aoh[IA], aow[IA], acl[IA];
-  bool aok[IA];
+  // LDS row of A-operand glds j -> its GEMM row's (n, a, b) and validity; the lane's (swizzled) channel chunk
+  auto a_row = [&](int j, int& n, int& oh, int& ow, bool& ok) {
+    const int m = m0 + (w * IA + j) * RPG + lane / CW;
+    ok = m < M;
+    const int mm = ok ? m : 0;
+    n = mm / (rowsH * rowsW);
+    const int rem = mm - n * rowsH * rowsW;
+    oh = rem / rowsW;
+    ow = rem - oh * rowsW;
+  };
+  int acl[IA];
 #pragma unroll
-  for (int j = 0; j < IA; ++j) {
-    const int r = (w * IA + j) * RPG + lane / CW;
-    const int m = m0 + r;
-    aok[j] = m < M;
-    const int mm = aok[j] ? m : 0;
-    an[j] = mm / (rowsH * rowsW);
-    const int rem = mm - an[j] * rowsH * rowsW;
-    aoh[j] = rem / rowsW;
-    aow[j] = rem - aoh[j] * rowsW;
-    acl[j] = cswz_k<CW>(r, lane % CW) * 8;
-  }
-  const bf16_t* pb[IB];
-  const bf16_t* pb2[IB];
-  int bcl[IB];
+  for (int j = 0; j < IA; ++j) acl[j] = cswz_k<CW>((w * IA + j) * RPG + lane / CW, lane % CW) * 8;
+  int bcl[IB], bn[IB];
   bool bok[IB];
 #pragma unroll
   for (int j = 0; j < IB; ++j) {
     const int r = (w * IB + j) * RPG + lane / CW;
     const int n = n0 + r;
     bok[j] = n < g.Ncols;
-    pb[j] = g.Wt + (long)(bok[j] ? n : 0) * g.Kred;
-    pb2[j] = g.Wt2 + (long)(bok[j] ? n : 0) * g.K2;  // (unused unless the downsample segment is fused)
+    bn[j] = bok[j] ? n : 0;
     bcl[j] = cswz_k<CW>(r, lane % CW) * 8;
   }
-  const float inv_IC = 1.f / g.IC, inv_S = 1.f / g.S, inv_ns = PAR ? 1.f / pc.ns : 1.f;
   const bf16_t* zero = reinterpret_cast<const bf16_t*>(mer_conv_zero16);
-  // class-local reduction index kk -> (ri, si, c) -> source; the weight operand's offset of the same kk
-  auto par_a_src = [&](int n, int hh, int ww, bool rowok, int kk) -> const bf16_t* {
-    if (!rowok || kk >= Kr) return zero;
-    if (kk >= Kr0)  // the fused downsample segment (class 0): its output pixel (hh, ww) is the input pixel (2hh, 2ww)
-      return g.X2 + (((long)n * g.IH + hh) * g.IW + ww) * g.K2 + (kk - Kr0);
-    const int tap = fdiv(kk, inv_IC), c = kk - tap * g.IC;
-    const int ri = fdiv(tap, inv_ns), si = tap - ri * pc.ns;
-    const int ih = hh + pc.dh0 - ri, iw = ww + pc.dw0 - si;
-    if (ih < 0 || ih >= g.IH || iw < 0 || iw >= g.IW) return zero;
-    return g.X + (((long)n * g.IH + ih) * g.IW + iw) * g.IC + c;
-  };
-  auto par_b_off = [&](int kk) -> int {
-    const int tap = fdiv(kk, inv_IC), c = kk - tap * g.IC;
-    const int ri = fdiv(tap, inv_ns), si = tap - ri * pc.ns;
-    return ((pc.r0 + 2 * ri) * g.S + pc.s0 + 2 * si) * g.IC + c;
-  };
-  auto stage = [&](int buf, int k0) {
-    bf16_t* la = smem + buf * BUF;
-    bf16_t* lb = la + BM_ * KS;
-#pragma unroll
-    for (int j = 0; j < IA; ++j) {
-      const bf16_t* src = PAR ? par_a_src(an[j], aoh[j], aow[j], aok[j], k0 + acl[j])
-                              : conv_a_src<DGRAD>(g, an[j], aoh[j], aow[j], aok[j], k0 + acl[j], inv_IC, inv_S);
-      glds16(src, la + (w * IA + j) * 512);
-    }
-#pragma unroll
-    for (int j = 0; j < IB; ++j) {
-      const int kk = k0 + bcl[j];
-      const bool ok = bok[j] && kk < Kr;
-      const bf16_t* src = !PAR ? pb[j] + kk : (kk >= Kr0 ? pb2[j] + (kk - Kr0) : pb[j] + par_b_off(kk));
-      glds16(ok ? src : zero, lb + (w * IB + j) * 512);
-    }
-  };
 
   f32x4 acc[FM][FN];
 #pragma unroll
@@ -1477,44 +1474,190 @@ __global__ __launch_bounds__(64 * WM * WN * KG, conv_pipe_wpe(WM * WN * KG, BM_,
   // this K-group's K-steps: [kb, kb + nk) of the tile's nk_all; every group runs the loop nkg times (the barriers are
   // workgroup-wide), a group with fewer steps idles through its last ones
   const int nk_all = (Kr + KS - 1) / KS;
-  const int nkg = (nk_all + KG - 1) / KG, kb = kg * nkg;
+  const int nkg = (nk_all + KG - 1) / KG, kb = __builtin_amdgcn_readfirstlane(kg * nkg);  // (kg is wave-uniform)
   const int nk = nk_all - kb < nkg ? (nk_all - kb > 0 ? nk_all - kb : 0) : nkg;
   const int kofs = kb * KS;
   constexpr int G = IA + IB;
   static_assert(STAGES >= 2 && STAGES <= 4, "ring depth");
+  // The ring: stage(buf) issues the DMAs of the NEXT K-step (the steps are staged strictly in order, kofs first) into
+  // slot buf.  Read and write slots advance as wrapping counters.
+  auto k_loop = [&](auto&& stage) {
 #pragma unroll
-  for (int p = 0; p < STAGES - 1; ++p)
-    if (p < nk) stage(p, kofs + p * KS);
-  CTP(1);
-  for (int kt = 0; kt < nkg; ++kt) {
-    const int left = nk - 1 - kt;
-    const int ahead = left < (STAGES - 2) ? left : (STAGES - 2);
-    wait_tiles_in_flight<G>(ahead);
-    lds_barrier();
-    if (kt + STAGES - 1 < nk) stage((kt + STAGES - 1) % STAGES, kofs + (kt + STAGES - 1) * KS);
-    if (KG > 1 && kt >= nk) continue;
-    const bf16_t* la = smem + (kt % STAGES) * BUF;
-    const bf16_t* lb = la + BM_ * KS;
+    for (int p = 0; p < STAGES - 1; ++p)
+      if (p < nk) stage(p);
+    int wslot = STAGES - 1, rslot = 0;
+    CTP(1);
+    for (int kt = 0; kt < nkg; ++kt) {
+      const int left = nk - 1 - kt;
+      const int ahead = left < (STAGES - 2) ? left : (STAGES - 2);
+      wait_tiles_in_flight<G>(ahead);
+      lds_barrier();
+      if (kt + STAGES - 1 < nk) stage(wslot);
+      wslot = wslot == STAGES - 1 ? 0 : wslot + 1;
+      const bf16_t* la = smem + rslot * BUF;
+      rslot = rslot == STAGES - 1 ? 0 : rslot + 1;
+      if (KG > 1 && kt >= nk) continue;
+      const bf16_t* lb = la + BM_ * KS;
 #pragma unroll
-    for (int s = 0; s < KS / 32; ++s) {
-      bf16x8 af[FM], bfr[FN];
+      for (int s = 0; s < KS / 32; ++s) {
+        bf16x8 af[FM], bfr[FN];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        const int r = wr * TM + i * 16 + fr;
-        af[i] = *reinterpret_cast<const bf16x8*>(la + r * KS + cswz_k<CW>(r, s * 4 + fq) * 8);
+        for (int i = 0; i < FM; ++i) {
+          const int r = wr * TM + i * 16 + fr;
+          af[i] = *reinterpret_cast<const bf16x8*>(la + r * KS + cswz_k<CW>(r, s * 4 + fq) * 8);
+        }
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          const int r = wc * TN + j * 16 + fr;
+          bfr[j] = *reinterpret_cast<const bf16x8*>(lb + r * KS + cswz_k<CW>(r, s * 4 + fq) * 8);
+        }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
       }
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int r = wc * TN + j * 16 + fr;
-        bfr[j] = *reinterpret_cast<const bf16x8*>(lb + r * KS + cswz_k<CW>(r, s * 4 + fq) * 8);
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
     }
+  };
+
+  // Fast address path: every channel count is a multiple of the K-step, so a K-step lies inside ONE tap -- the tap, its
+  // element offset in the source window and the weight offset are wave-uniform and walk in scalar registers; a lane
+  // keeps, per DMA, the pointer of its row's window origin (+ its channel chunk; it may lie outside the tensor and is
+  // only ever an operand of a select) and one bit per tap, set where the tap's pixel is inside the frame.  Per K-step
+  // and DMA that leaves a bit test, a 64-bit add of a scalar and a select against the zero chunk.  Same sources in the
+  // same order as the generic staging below (kept for IC of 8 / 16, K tails, more than 32 taps -- a 7 x 7 forward; its
+  // stride-2 input gradient has 16 taps per parity class and walks).
+  // Two instantiations, not one kernel with both loops: the accumulators merging from two loops made the 128-VGPR
+  // parity-class 128 x 128 tile spill in its epilogue.
+  if constexpr (FAST) {
+    const bool has_ds = PAR && Kr > Kr0;  // this class carries the fused downsample segment
+    constexpr bool NEG = DGRAD || PAR;  // input gradients walk the window backwards
+    const int nr = PAR ? pc.nr : g.R, ns = PAR ? pc.ns : g.S;
+    const bf16_t* fa[IA];
+    unsigned fm[IA];
+#pragma unroll
+    for (int j = 0; j < IA; ++j) {
+      int n, oh, ow;
+      bool ok;
+      a_row(j, n, oh, ow, ok);
+      // window origin: tap (ri, si) reads pixel (h0 + sg * ri, w0 + sg * si)
+      const int h0 = PAR ? oh + pc.dh0 : DGRAD ? oh + g.pad : oh * g.st - g.pad;
+      const int w0 = PAR ? ow + pc.dw0 : DGRAD ? ow + g.pad : ow * g.st - g.pad;
+      unsigned cm = 0, m = 0;
+      for (int si = 0; si < ns; ++si) cm |= (unsigned)((unsigned)(NEG ? w0 - si : w0 + si) < (unsigned)g.IW) << si;
+      for (int ri = 0; ri < nr; ++ri)
+        if ((unsigned)(NEG ? h0 - ri : h0 + ri) < (unsigned)g.IH) m |= cm << (ri * ns);
+      fm[j] = ok ? m : 0u;
+      fa[j] = g.X + ((((long)n * g.IH + h0) * g.IW + w0) * g.IC + acl[j]);
+    }
+    const bf16_t* fb[IB];
+#pragma unroll
+    for (int j = 0; j < IB; ++j) fb[j] = g.Wt + ((long)bn[j] * g.Kred + bcl[j]);
+    // the scalar walk: tap (ri, si), channel base c inside it, the tap's A / weight element offsets
+    int f_ic = g.IC, f_c, f_tap, f_ri, f_si, f_aoff, f_boff;
+    bool f_ds = false;
+    auto tap_offsets = [&]() {
+      const int ao = (f_ri * g.IW + f_si) * g.IC;
+      f_aoff = NEG ? -ao : ao;
+      f_boff = PAR ? ((pc.r0 + 2 * f_ri) * g.S + pc.s0 + 2 * f_si) * g.IC : f_tap * g.IC;
+    };
+    // class 0's downsample segment: one tap, valid wherever the row is; its output pixel (hh, ww) is the input pixel
+    auto enter_ds = [&]() {
+      f_ds = true;
+      f_ic = g.K2;
+      f_c = f_tap = f_ri = f_si = f_aoff = f_boff = 0;
+#pragma unroll
+      for (int j = 0; j < IA; ++j) {
+        int n, hh, ww;
+        bool ok;
+        a_row(j, n, hh, ww, ok);
+        fm[j] = ok ? 1u : 0u;
+        fa[j] = g.X2 + ((((long)n * g.IH + hh) * g.IW + ww) * g.K2 + acl[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < IB; ++j) fb[j] = g.Wt2 + ((long)bn[j] * g.K2 + bcl[j]);
+    };
+    if (has_ds && kofs >= Kr0) {
+      enter_ds();
+      f_c = kofs - Kr0;
+    } else {
+      f_tap = kofs / g.IC;
+      f_c = kofs - f_tap * g.IC;
+      f_ri = f_tap / (ns > 0 ? ns : 1);  // (a parity class of a 1 x 1 conv can be empty: no taps, no K-steps)
+      f_si = f_tap - f_ri * ns;
+      tap_offsets();
+    }
+    k_loop([&](int buf) {
+      bf16_t* la = smem + buf * BUF;
+      bf16_t* lb = la + BM_ * KS;
+      const unsigned tbit = 1u << (f_tap & 31);
+      const long ao = f_aoff + f_c, bo = f_boff + f_c;
+#pragma unroll
+      for (int j = 0; j < IA; ++j) glds16((fm[j] & tbit) ? fa[j] + ao : zero, la + (w * IA + j) * 512);
+#pragma unroll
+      for (int j = 0; j < IB; ++j) glds16(bok[j] ? fb[j] + bo : zero, lb + (w * IB + j) * 512);
+      f_c += KS;
+      if (f_c == f_ic) {  // (wave-uniform) next tap
+        f_c = 0;
+        ++f_tap;
+        if (++f_si == ns) {
+          f_si = 0;
+          ++f_ri;
+        }
+        tap_offsets();
+        if (has_ds && !f_ds && f_tap == nr * ns) enter_ds();
+      }
+    });
+  } else {
+    int an[IA], aoh[IA], aow[IA];
+    bool aok[IA];
+#pragma unroll
+    for (int j = 0; j < IA; ++j) a_row(j, an[j], aoh[j], aow[j], aok[j]);
+    const bf16_t* pb[IB];
+    const bf16_t* pb2[IB];
+#pragma unroll
+    for (int j = 0; j < IB; ++j) {
+      pb[j] = g.Wt + (long)bn[j] * g.Kred;
+      pb2[j] = g.Wt2 + (long)bn[j] * g.K2;  // (unused unless the downsample segment is fused)
+    }
+    const float inv_IC = 1.f / g.IC, inv_S = 1.f / g.S, inv_ns = PAR ? 1.f / pc.ns : 1.f;
+    // class-local reduction index kk -> (ri, si, c) -> source; the weight operand's offset of the same kk
+    auto par_a_src = [&](int n, int hh, int ww, bool rowok, int kk) -> const bf16_t* {
+      if (!rowok || kk >= Kr) return zero;
+      if (kk >= Kr0)  // the fused downsample segment (class 0): its output pixel (hh, ww) is the input pixel (2hh, 2ww)
+        return g.X2 + (((long)n * g.IH + hh) * g.IW + ww) * g.K2 + (kk - Kr0);
+      const int tap = fdiv(kk, inv_IC), c = kk - tap * g.IC;
+      const int ri = fdiv(tap, inv_ns), si = tap - ri * pc.ns;
+      const int ih = hh + pc.dh0 - ri, iw = ww + pc.dw0 - si;
+      if (ih < 0 || ih >= g.IH || iw < 0 || iw >= g.IW) return zero;
+      return g.X + (((long)n * g.IH + ih) * g.IW + iw) * g.IC + c;
+    };
+    auto par_b_off = [&](int kk) -> int {
+      const int tap = fdiv(kk, inv_IC), c = kk - tap * g.IC;
+      const int ri = fdiv(tap, inv_ns), si = tap - ri * pc.ns;
+      return ((pc.r0 + 2 * ri) * g.S + pc.s0 + 2 * si) * g.IC + c;
+    };
+    int k0 = kofs;
+    k_loop([&](int buf) {
+      bf16_t* la = smem + buf * BUF;
+      bf16_t* lb = la + BM_ * KS;
+#pragma unroll
+      for (int j = 0; j < IA; ++j) {
+        const bf16_t* src = PAR ? par_a_src(an[j], aoh[j], aow[j], aok[j], k0 + acl[j])
+                                : conv_a_src<DGRAD>(g, an[j], aoh[j], aow[j], aok[j], k0 + acl[j], inv_IC, inv_S);
+        glds16(src, la + (w * IA + j) * 512);
+      }
+#pragma unroll
+      for (int j = 0; j < IB; ++j) {
+        const int kk = k0 + bcl[j];
+        const bool ok = bok[j] && kk < Kr;
+        const bf16_t* src = !PAR ? pb[j] + kk : (kk >= Kr0 ? pb2[j] + (kk - Kr0) : pb[j] + par_b_off(kk));
+        glds16(ok ? src : zero, lb + (w * IB + j) * 512);
+      }
+      k0 += KS;
+    });
   }
   CTP(2);
 
@@ -1724,24 +1867,24 @@ int launch_conv_pipe_t(ConvGeom& g, hipStream_t st) {
   if (KG > 1 && !g.vec) return (int)hipErrorInvalidValue;  // the split-K form has the 16-byte epilogue only
   // a stride-1 input gradient whose BN-backward target has no second (downsample) branch runs the instantiation
   // without the x2 terms: 24 fewer VGPRs, which keeps the 8-wave tiles at 2 blocks per CU
+  // every reduction segment a whole number of K-steps long and at most 32 taps (one validity bit each; PAR: the
+  // taps of the largest parity class): the scalar-walk staging (FAST)
+  const bool fast = PAR ? (g.IC % KS == 0 && (!g.X2 || g.K2 % KS == 0) && ((g.R + 1) / 2) * ((g.S + 1) / 2) <= 32)
+                        : (g.IC % KS == 0 && g.R * g.S <= 32 && (!DGRAD || g.st == 1));
+  auto launch = [&](void (*kern)(ConvGeom), unsigned gy) -> int {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+      return (int)hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, gy), dim3(64 * WM * WN * KG), lds, st, g);
+    return (int)hipGetLastError();
+  };
   if constexpr (DGRAD && !PAR) {
-    if (!g.bnr_x2) {
-      if (hipFuncSetAttribute(
-              reinterpret_cast<const void*>(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, false, KG>),
-              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return (int)hipErrorInvalidConfiguration;
-      hipLaunchKernelGGL((conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, false, KG>),
-                         dim3((unsigned)tiles, 1), dim3(64 * WM * WN * KG), lds, st, g);
-      return (int)hipGetLastError();
-    }
+    if (!g.bnr_x2)
+      return fast ? launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, false, KG, true>, 1)
+                  : launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, false, KG, false>, 1);
   }
-  if (hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, true, KG>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return (int)hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL((conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, true, KG>),
-                     dim3((unsigned)tiles, PAR ? 4 : 1), dim3(64 * WM * WN * KG), lds, st, g);
-  return (int)hipGetLastError();
+  return fast ? launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, true, KG, true>, PAR ? 4 : 1)
+              : launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, true, KG, false>, PAR ? 4 : 1);
 }
 
 // variant 1: 4-wave tiles; variant 2 (default): 8-wave tiles -- more waves per CU hide the DMA latency of
