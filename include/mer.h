@@ -445,7 +445,14 @@ int mer_partials_sum2(int C, int parts, float* in, float* out, float* in2, float
  * (splits*K*R*S*C floats), then a reduce pass sums the slabs into dw (deterministic, no atomics). */
 int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad, const void* x,
                    const void* dy, float* dw, int splits, float* workspace, void* stream);
-/* mer_conv_wgrad with an explicit kernel: -1 auto, 1 4-wave tiles, 2 8-wave tiles (the default). */
+/* mer_conv_wgrad with an explicit kernel: -1 auto, 1 4-wave tiles, 2 8-wave tiles, 3 with a 2-deep register prefetch,
+ * 4-7 the global_load_lds rings, 8 two K-groups per workgroup.  1-7 give the same bits; 8 agrees to fp32 rounding.
+ * 9 / 10: the strip kernel for 3x3 / stride-1 / pad-1 convs -- all nine taps of a (64 / 32 output channels) x (64
+ * input channels) tile from one LDS strip of X rows, the reduction over a padded pixel index (rows of W + 1 slots, one
+ * pad row per image).  Its splits are ranges of image rows: N * (H + 1) rows in ceil(rows / splits)-row pieces, every
+ * split non-empty, so it may use fewer than `splits` (never more; the workspace bound holds).  Same slab layout and
+ * fold; a different fp32 summation order, so it agrees with 1-8 to fp32 rounding.  hipErrorInvalidValue unless R = S =
+ * 3, stride = pad = 1, C % 64 == 0, K % 64 (9) or K % 32 (10) == 0, Creal == C and W <= 126; -1 never picks it. */
 int mer_conv_wgrad_ex(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad, const void* x,
                       const void* dy, float* dw, int splits, float* workspace, int variant, void* stream);
 /* The split-K pass of mer_conv_wgrad alone: workspace = splits x [K][R*S*C] fp32 partial slabs, folded later by

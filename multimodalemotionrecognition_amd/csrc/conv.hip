@@ -48,6 +48,14 @@ MER_API int mer_ctp_reset() {
 MER_API int mer_ctp_read(long long* host) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(mer_ctp_buf), sizeof(long long) * 4096 * 8, 0, hipMemcpyDeviceToHost);
 }
+// Diagnostic forms of the weight-gradient K loops (tools/pipe_phases.py wgrad --bound; results WRONG): 1 = no LDS-DMA
+// issue after the prologue (what the loop costs without operand fill), 2 = the fragment reads of the first K-step
+// only (what it costs without LDS reads).  The production library compiles CT_MODE() to the constant 0.
+static __device__ int mer_ct_mode_v;
+#define CT_MODE() mer_ct_mode_v
+MER_API int mer_ct_mode(int mode) {
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(mer_ct_mode_v), &mode, sizeof(int), 0, hipMemcpyHostToDevice);
+}
 #else
 #define CT(k) \
   do { \
@@ -55,6 +63,7 @@ MER_API int mer_ctp_read(long long* host) {
 #define CTP(k) \
   do { \
   } while (0)
+#define CT_MODE() 0
 #endif
 
 namespace {
@@ -439,6 +448,28 @@ __device__ __attribute__((aligned(16))) uint32_t mer_conv_zero16[4] = {0u, 0u, 0
 
 __device__ __forceinline__ int wswz(int row, int nchunks) { return ((row & 7) << 1) & (nchunks - 1); }
 
+// ds_read_b64_tr_b16 beside LDS-DMAs in flight.  Through the builtin, hipcc waits vmcnt(0) before the first transposed
+// read after a global_load_lds (it cannot tell the ring slot being read from the one being filled): the K loops below
+// issued the next K-step's DMAs and then drained them before reading the current one -- no K-step of fill ever
+// overlapped compute (the .s of wgrad_pipe_kernel had `s_waitcnt vmcnt(0)` ahead of each K-step's reads; without the
+// per-step DMA issue the layer1 K-step took 0.68 us instead of 1.11, profiles/r08/wgrad_bound.txt).  As inline asm the
+// read carries no memory operand, so the counted vmcnt waits of the loop are the only ones; the compiler then does
+// not count these reads on lgkmcnt either: lds_tr_wait<N>() + frag_ready() before the first use of a fragment.
+__device__ __forceinline__ s16x4 lds_read_tr16(const void* p) {
+  typedef __attribute__((address_space(3))) const char lds_cchar;
+  const uint32_t a = (uint32_t)(uintptr_t)(lds_cchar*)p;
+  s16x4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a) : "memory");
+  return v;
+}
+// at most N LDS reads of this wave still in flight (they return in order)
+template <int N>
+__device__ __forceinline__ void lds_tr_wait() {
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
+// orders every use of f after the volatile asm statements before this one (the wait)
+__device__ __forceinline__ void frag_ready(bf16x8& f) { asm volatile("" : "+v"(f)); }
+
 // KG > 1: in-workgroup split-K over the pixels, as in conv_pipe_kernel: KG groups of WM x WN waves, each with its own
 // ring and a contiguous 1/KG of the split's K-steps; the groups' tiles are summed in LDS in group order before the one
 // slab store.  A KG = 2 launch covers the pixels of two one-group splits with the same waves per CU, so it writes (and
@@ -562,12 +593,9 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
     const int q = (lane & 15) >> 2, p4 = (lane & 3) * 4;
     const int kr = k0 + 8 * (lane >> 4);
     const int lc = (c0 + p4) >> 3, sub = (c0 + p4) & 7;
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const int r0 = kr + q, r1 = kr + 4 + q;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_s16x4*)(img + r0 * CW * 8 + ((lc ^ wswz(r0, CW)) << 3) + sub));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_s16x4*)(img + r1 * CW * 8 + ((lc ^ wswz(r1, CW)) << 3) + sub));
+    const s16x4 lo = lds_read_tr16(img + r0 * CW * 8 + ((lc ^ wswz(r0, CW)) << 3) + sub);
+    const s16x4 hi = lds_read_tr16(img + r1 * CW * 8 + ((lc ^ wswz(r1, CW)) << 3) + sub);
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
@@ -583,13 +611,16 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
   for (int s = 0; s < STAGES - 1; ++s)
     if (s < nk) stage(s);
   int wslot = STAGES - 1, rslot = 0;  // ring slots: wrapping counters
+#ifdef MER_CONV_TIMING
+  bf16x8 af_h[KS / 32][IT] = {}, bfr_h[KS / 32][JT] = {};  // CT_MODE() 2: the first K-step's fragments, reused
+#endif
   CTP(1);
   for (int kt = 0; kt < nkg; ++kt) {
     const int left = nk - 1 - kt;
     const int ahead = left < (STAGES - 2) ? left : (STAGES - 2);
     wait_tiles_in_flight<G>(ahead);
     lds_barrier();
-    if (kt + STAGES - 1 < nk) stage(wslot);
+    if (kt + STAGES - 1 < nk && CT_MODE() != 1) stage(wslot);
     wslot = wslot == STAGES - 1 ? 0 : wslot + 1;
     const bf16_t* Aimg = smem + rslot * BUF;
     rslot = rslot == STAGES - 1 ? 0 : rslot + 1;
@@ -598,10 +629,33 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
 #pragma unroll
     for (int s = 0; s < KS / 32; ++s) {
       bf16x8 af[IT], bfr[JT];
+#ifdef MER_CONV_TIMING
+      if (CT_MODE() == 2 && kt > 0) {
 #pragma unroll
-      for (int i = 0; i < IT; ++i) af[i] = tr_frag(Aimg, ACW, s * 32, wm + i * 16);
+        for (int i = 0; i < IT; ++i) af[i] = af_h[s][i];
 #pragma unroll
-      for (int j = 0; j < JT; ++j) bfr[j] = tr_frag(Bimg, BCW, s * 32, wn + j * 16);
+        for (int j = 0; j < JT; ++j) bfr[j] = bfr_h[s][j];
+      } else
+#endif
+      {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) af[i] = tr_frag(Aimg, ACW, s * 32, wm + i * 16);
+#pragma unroll
+        for (int j = 0; j < JT; ++j) bfr[j] = tr_frag(Bimg, BCW, s * 32, wn + j * 16);
+        lds_tr_wait<0>();
+#pragma unroll
+        for (int i = 0; i < IT; ++i) frag_ready(af[i]);
+#pragma unroll
+        for (int j = 0; j < JT; ++j) frag_ready(bfr[j]);
+      }
+#ifdef MER_CONV_TIMING
+      if (kt == 0) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) af_h[s][i] = af[i];
+#pragma unroll
+        for (int j = 0; j < JT; ++j) bfr_h[s][j] = bfr[j];
+      }
+#endif
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < IT; ++i)
@@ -669,6 +723,280 @@ void launch_wgrad_pipe(const WgradGeom& g0, dim3 grid, hipStream_t st) {
   g.flat = 1;
   const dim3 gr(grid.x * grid.z, 1, 1);
   hipLaunchKernelGGL((wgrad_pipe_kernel<BM_, BN_, WM, WN, STAGES, KS, KG>), gr, dim3(64 * WM * WN * KG), lds, st, g);
+}
+
+// ---------------------------------------------------------------------------------------
+// Strip weight gradient of a 3x3 / stride-1 / pad-1 conv (variants 9 and 10): all nine taps from ONE LDS strip.
+// wgrad_pipe_kernel tiles the (tap, c) axis over workgroups, so every 64x128 tile DMAs its own dY tile and its own
+// shifted X window each K-step: layer1 filled LDS with ~376 MB per launch for 51 MB of operands, and the nine taps'
+// windows are the same rows shifted by a pixel or an image row.  Here the reduction runs over a PADDED pixel index q:
+// an image is H rows of W + 1 slots (slot W is the pad column -- one row's right pad and the next row's left pad)
+// followed by one pad row, so in q space tap (r, s) is the constant shift (r - 1) * (W + 1) + (s - 1) and every
+// border tap, the corners and the image seams included, lands on a pad slot:
+//   dw[k][(r, s, c)] = sum_q dY[q][k] * X[q + (r - 1) * (W + 1) + (s - 1)][c],  dY = X = 0 at pad slots
+// (pad slots DMA the 16-byte zero chunk: validity is evaluated unconditionally and feeds a select).  The cost is
+// (H + 1)(W + 1) / (H W) more K: 7 % at 28x28, 15 % at 14x14.
+// A workgroup owns a (KB output channels) x (9 taps x 64 input channels) tile of one split.  X rows stream through a
+// ring of `xrows` LDS rows [q][64 channels] addressed by (stream row & (xrows - 1)); a K-step of 64 slots DMAs 64 new
+// X rows and its 64 dY rows ([q][KB], a STAGES-deep ring) and reads rows [64 kt, 64 kt + 64 + 2 (W + 2)) of the X
+// stream, which begins W + 2 rows before the split.  12 waves = (tap row r) x (16-channel quarter): a wave reads its dY
+// fragments once per 32 slots and serves its three taps s = 0..2 from the strip at row base r (W + 1) + s with
+// ds_read_b64_tr_b16 -- per K-step 2 x (KB/16 + 3) fragments for 2 x 3 KB/16 MFMAs.  Rows of 8 (4) 16-byte chunks
+// are XOR-swizzled by row bits 1 and 3 (bit 3): the 8 rows {b..b+3, b+8..b+11} one 32-lane half of a transposed read
+// touches then cover all 64 banks for any row base b.  Splits are ranges of image rows (pad rows included); the
+// slabs are wgrad_pipe_kernel's [split][K][tap * C + c], the grid its split-major XCD order.
+struct StripGeom {
+  int N, H, W, C, K;
+  const bf16_t* X;
+  const bf16_t* dY;
+  float* ws;
+  int ldy;
+  int rows_per_split;  // image rows (pad rows included) per split
+  int xrows;           // rows of the X ring: a power of two >= 64 * (ceil(2 (W + 2) / 64) + STAGES)
+};
+
+__device__ __forceinline__ int sswz(int row, int nchunks) {
+  return nchunks == 8 ? ((row & 2) | ((row >> 1) & 4)) : ((row >> 2) & 2);
+}
+
+// one DMA instruction's lane state: the source of this lane's 16 bytes (row `u` of the operand's stream, at padded
+// slot (n, h, w)), walked 64 slots per issue with two bounded carries as in wgrad_pipe_kernel
+struct StripUnit {
+  const bf16_t* p;
+  int n, h, w, u, lim, stride, wstride, dstep;
+};
+
+template <int KB, int STAGES>
+__global__ __launch_bounds__(768, 3) void wgrad_strip_kernel(StripGeom g) {
+  constexpr int KS = 64, NW = 12;
+  constexpr int ACW = KB / 8;    // 16-byte chunks per dY row
+  constexpr int ARI = 64 / ACW;  // dY rows per DMA instruction
+  constexpr int NDU = KS / ARI;  // dY DMA instructions per K-step (the X chunk takes 8)
+  constexpr int IT = KB / 16;
+  constexpr int ABUF = KS * KB;  // bf16 elements per dY ring slot
+  static_assert(NDU >= NW - 8 && 8 + NDU <= 2 * NW, "8 X + NDU dY instructions over 12 waves, one or two each");
+  static_assert(STAGES >= 2 && STAGES <= 4, "vmcnt waits below cover (STAGES - 2) * 2 <= 4");
+  extern __shared__ __attribute__((aligned(16))) bf16_t smem_all[];
+  bf16_t* const xring = smem_all;
+  bf16_t* const aring = smem_all + g.xrows * 64;
+  const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
+  CTP(0);
+  const int Wp = g.W + 1, Hp = g.H + 1, IQ = Hp * Wp, HL = Wp + 1;
+  const int Ntot = 9 * g.C;
+  const int nct = g.C / 64, ntile = nct * (g.K / KB);
+  int tile, zs;
+  xcd_tile(blockIdx.x, ntile, (int)gridDim.x, tile, zs);
+  const int kti = tile / nct, cti = tile - kti * nct;
+  const int k0 = kti * KB, c0 = cti * 64;
+  const int TR = g.N * Hp;
+  const int rb = zs * g.rows_per_split, re = min(TR, rb + g.rows_per_split);
+  const int qb = rb * Wp, qlen = (re - rb) * Wp;
+  const int nk = (qlen + KS - 1) / KS;
+  const int NH = (2 * HL + KS - 1) / KS;  // X chunks a K-step reads beyond its own
+  const int xmask = g.xrows - 1;
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(mer_conv_zero16);
+
+  const int s_dn = KS / IQ, s_rem = KS - s_dn * IQ, s_dh = s_rem / Wp, s_dw = s_rem - s_dh * Wp;
+  auto unit_init = [&](bool isx, int ui) -> StripUnit {
+    StripUnit a;
+    int row, chunk;
+    if (isx) {
+      row = ui * 8 + (lane >> 3);
+      chunk = (lane & 7) ^ sswz(row, 8);
+      a.stride = g.C;
+      a.lim = qlen + 2 * HL;
+    } else {
+      row = ui * ARI + lane / ACW;
+      chunk = (lane % ACW) ^ sswz(row, ACW);
+      a.stride = g.ldy;
+      a.lim = qlen;
+    }
+    const int qq = qb + row - (isx ? HL : 0) + IQ;  // >= 0: the first image's halo lies in "image -1"
+    const int n1 = qq / IQ, rem = qq - n1 * IQ;
+    a.n = n1 - 1;
+    a.h = rem / Wp;
+    a.w = rem - a.h * Wp;
+    a.u = row;
+    a.wstride = g.W * a.stride;
+    a.dstep = ((s_dn * g.H + s_dh) * g.W + s_dw) * a.stride;
+    // (outside the tensor at pad slots: then only ever an operand of the select against the zero chunk)
+    a.p = (isx ? g.X + c0 : g.dY + k0) + (((long)a.n * g.H + a.h) * g.W + a.w) * a.stride + chunk * 8;
+    return a;
+  };
+  auto issue = [&](StripUnit& a, bf16_t* dst) {
+    const int ok = (int)(a.u < a.lim) & (int)((unsigned)a.n < (unsigned)g.N) & (int)(a.h < g.H) & (int)(a.w < g.W);
+    glds16(ok ? a.p : zero, dst);
+    a.u += KS;
+    int d = a.dstep;
+    a.w += s_dw;
+    const bool cw = a.w >= Wp;  // w -= W + 1, h += 1
+    a.w -= cw ? Wp : 0;
+    d -= cw ? a.stride : 0;
+    a.h += s_dh + (cw ? 1 : 0);
+    const bool ch = a.h >= Hp;  // h -= H + 1, n += 1
+    a.h -= ch ? Hp : 0;
+    d -= ch ? a.wstride : 0;
+    a.n += s_dn + (ch ? 1 : 0);
+    a.p += d;
+  };
+  // DMA instruction `unit` of a K-step: 0..7 the X chunk's 8-row groups, 8.. the dY rows.  Wave w issues unit w and,
+  // where there is one, unit w + 12 (always dY).
+  const bool s0x = w < 8;
+  const bool has1 = NDU > NW - 8 && w + NW - 8 < NDU;
+  StripUnit u0 = unit_init(s0x, s0x ? w : w - 8);
+  StripUnit u1 = unit_init(false, has1 ? w + NW - 8 : 0);
+  int xw = 0;  // ring row of the next X chunk
+  auto stage_x = [&]() {
+    if (s0x) issue(u0, xring + (xw + w * 8) * 64);
+    xw = (xw + KS) & xmask;
+  };
+  auto stage = [&](int aslot) {  // K-step j: X chunk j + NH and dY chunk j
+    bf16_t* la = aring + aslot * ABUF;
+    stage_x();
+    if (!s0x) issue(u0, la + (w - 8) * 512);
+    if (has1) issue(u1, la + (w + NW - 8) * 512);
+  };
+
+  // fragment addresses (bytes from the ring bases): the dY ones are fixed per ring slot; an X row is
+  // (64 kt + fixed) & xmask, and its swizzle reads row bits 1 and 3 only, so the column part is fixed too
+  const int g4 = lane >> 4, fq = (lane & 15) >> 2, p4 = (lane & 3) * 4;
+  const int tr = w >> 2, cq = w & 3;  // this wave's tap row and channel quarter
+  int aoff[2][2][IT], xrow[3][2][2], xcol[3][2][2];
+#pragma unroll
+  for (int ss = 0; ss < 2; ++ss)
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi) {
+      const int row = ss * 32 + 8 * g4 + 4 * hi + fq;
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int col = i * 16 + p4;
+        aoff[ss][hi][i] = (row * KB + ((((col >> 3) ^ sswz(row, ACW))) << 3) + (col & 7)) * 2;
+      }
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int xr = row + tr * Wp + s;
+        const int col = cq * 16 + p4;
+        xrow[s][ss][hi] = xr * 128;
+        xcol[s][ss][hi] = (((((col >> 3) ^ sswz(xr, 8))) << 3) + (col & 7)) * 2;
+      }
+    }
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  auto frag = [&](const char* lo_p, const char* hi_p) -> bf16x8 {
+    const s16x4 lo = lds_read_tr16(lo_p);
+    const s16x4 hi = lds_read_tr16(hi_p);
+    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+  };
+
+  f32x4 acc[3][IT];
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int i = 0; i < IT; ++i) acc[s][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const char* const Xb = reinterpret_cast<const char*>(xring);
+  auto read_frags = [&](int ss, const char* Ab, int xbB, bf16x8* af, bf16x8* bfr) {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) af[i] = frag(Ab + aoff[ss][0][i], Ab + aoff[ss][1][i]);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+      bfr[s] = frag(Xb + (((xbB + xrow[s][ss][0]) & (g.xrows * 128 - 1)) + xcol[s][ss][0]),
+                    Xb + (((xbB + xrow[s][ss][1]) & (g.xrows * 128 - 1)) + xcol[s][ss][1]));
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  constexpr int NFR = 2 * (IT + 3);  // LDS reads of one fragment set
+  auto frags_ready = [&](bf16x8* af, bf16x8* bfr) {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) frag_ready(af[i]);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) frag_ready(bfr[s]);
+  };
+  auto mfma_all = [&](const bf16x8* af, const bf16x8* bfr) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int i = 0; i < IT; ++i) acc[s][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[s], acc[s][i], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  bf16x8 af0[IT], bf0[3], af1[IT] = {}, bf1[3] = {};
+
+  for (int pc = 0; pc < NH; ++pc) stage_x();  // the X stream's first NH chunks: the halo before the split
+#pragma unroll
+  for (int s = 0; s < STAGES - 1; ++s)
+    if (s < nk) stage(s);
+  int wslot = STAGES - 1, rslot = 0;
+  const int xmaskB = g.xrows * 128 - 1;
+  int xbB = 0;  // byte offset of stream row 64 kt in the X ring
+  const int gw = has1 ? 2 : 1;  // this wave's DMAs per stage
+  CTP(1);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int left = nk - 1 - kt;
+    const int fly = (left < (STAGES - 2) ? left : (STAGES - 2)) * gw;  // own DMAs that may stay in flight
+    if (fly <= 0) wait_vmcnt<0>();
+    else if (fly == 1) wait_vmcnt<1>();
+    else if (fly == 2) wait_vmcnt<2>();
+    else wait_vmcnt<4>();
+    lds_barrier();
+    if (kt + STAGES - 1 < nk && CT_MODE() != 1) stage(wslot);
+    wslot = wslot == STAGES - 1 ? 0 : wslot + 1;
+    const char* Ab = reinterpret_cast<const char*>(aring + rslot * ABUF);
+    rslot = rslot == STAGES - 1 ? 0 : rslot + 1;
+    // two fragment sets, the reads one half-step ahead of the MFMAs: every wave reads right after the barrier, so
+    // without MFMAs to issue meanwhile the LDS time of all 12 waves' reads was exposed in every half-step
+    frags_ready(af1, bf1);  // set 1's reads of K-step kt - 1 retired at the barrier's lgkmcnt(0)
+    if (CT_MODE() != 2 || kt == 0) read_frags(0, Ab, xbB, af0, bf0);
+    mfma_all(af1, bf1);  // half-step 1 of K-step kt - 1 (zeros before the first)
+    if (CT_MODE() != 2 || kt == 0) read_frags(1, Ab, xbB, af1, bf1);
+    lds_tr_wait<NFR>();  // set 0 has landed, set 1 may still be in flight
+    frags_ready(af0, bf0);
+    mfma_all(af0, bf0);
+    xbB = (xbB + KS * 128) & xmaskB;
+  }
+  lds_tr_wait<0>();
+  frags_ready(af1, bf1);
+  mfma_all(af1, bf1);
+  CTP(2);
+  CTP(3);
+  float* slab = g.ws + (long)zs * g.K * Ntot;
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int nn = (tr * 3 + s) * g.C + c0 + cq * 16 + (lane & 15);
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) slab[(long)(k0 + i * 16 + g4 * 4 + rr) * Ntot + nn] = acc[s][i][rr];
+    }
+  CTP(4);
+}
+
+// launches the strip kernel over `splits` row ranges (in: requested, out: the count used -- every split non-empty);
+// hipErrorInvalidValue where the X ring would not fit (W > 126) or the padded index leaves 31 bits
+template <int KB>
+int launch_wgrad_strip(const WgradGeom& g0, int& splits, hipStream_t st) {
+  constexpr int STAGES = 4;
+  StripGeom g{};
+  g.N = g0.N; g.H = g0.H; g.W = g0.W; g.C = g0.C; g.K = g0.K;
+  g.X = g0.X; g.dY = g0.dY; g.ws = g0.ws; g.ldy = (int)g0.ldy;
+  const int Wp = g.W + 1, Hp = g.H + 1;
+  const long TR = (long)g.N * Hp;
+  if (g0.ldy >= (1 << 24) || (TR + Hp) * Wp >= (1L << 30)) return (int)hipErrorInvalidValue;
+  const int chunks = (2 * (Wp + 1) + 63) / 64 + STAGES;
+  int xc = 1;
+  while (xc < chunks) xc *= 2;
+  if (xc > 8) return (int)hipErrorInvalidValue;
+  g.xrows = xc * 64;
+  if (splits < 1) splits = 1;
+  g.rows_per_split = (int)((TR + splits - 1) / splits);
+  splits = (int)((TR + g.rows_per_split - 1) / g.rows_per_split);
+  const size_t lds = ((size_t)g.xrows * 64 + (size_t)STAGES * 64 * KB) * sizeof(bf16_t);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_strip_kernel<KB, STAGES>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return (int)hipErrorInvalidValue;
+  const int tiles = (g.C / 64) * (g.K / KB);
+  hipLaunchKernelGGL((wgrad_strip_kernel<KB, STAGES>), dim3(splits * tiles), dim3(768), lds, st, g);
+  return (int)hipSuccess;
 }
 
 // slab0[i] = sum_z ws[z][i] over the flat [K][R*S*C] index.  A block owns E = 256/SG consecutive elements
@@ -2396,8 +2724,13 @@ MER_API int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, 
 static int conv_wgrad_impl(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
                            const void* x, const void* dy, long ldy, float* dw, int splits, float* workspace,
                            int variant, void* stream, bool fold = true) {
-  if (C % 8 || K % 8 || variant < -1 || variant > 8 || R * S > 49) return (int)hipErrorInvalidValue;
+  if (C % 8 || K % 8 || variant < -1 || variant > 10 || R * S > 49) return (int)hipErrorInvalidValue;
   if (variant == -1) variant = wgrad_default_variant(K);
+  // the strip kernel (9: 64 output channels per tile, 10: 32) takes 3x3 / stride-1 / pad-1 convs on whole 64-channel
+  // chunks only
+  const bool strip = variant == 9 || variant == 10;
+  if (strip && (R != 3 || S != 3 || stride != 1 || pad != 1 || C % 64 || K % (variant == 9 ? 64 : 32) || Creal != C))
+    return (int)hipErrorInvalidValue;
   WgradGeom g{};
   g.N = N; g.H = H; g.W = W; g.C = C; g.Creal = Creal;
   g.Ho = (H + 2 * pad - R) / stride + 1; g.Wo = (W + 2 * pad - S) / stride + 1; g.K = K;
@@ -2405,12 +2738,17 @@ static int conv_wgrad_impl(int N, int H, int W, int C, int Creal, int K, int R, 
   g.X = (const bf16_t*)x; g.dY = (const bf16_t*)dy; g.ws = workspace;
   g.ldy = ldy > 0 ? ldy : K;
   const int P = N * g.Ho * g.Wo;
+  const int splits_req = splits;
   if (splits < 1) splits = 1;
   g.pix_per_split = ((P + splits - 1) / splits + 63) / 64 * 64;
   splits = (P + g.pix_per_split - 1) / g.pix_per_split;  // every split non-empty (<= requested)
   const int Ntot = R * S * C;
   hipStream_t st = (hipStream_t)stream;
-  if (K <= 64) {
+  if (strip) {  // splits are ranges of image rows there: `splits` becomes the count it used
+    splits = splits_req;
+    const int rc = variant == 9 ? launch_wgrad_strip<64>(g, splits, st) : launch_wgrad_strip<32>(g, splits, st);
+    if (rc != (int)hipSuccess) return rc;
+  } else if (K <= 64) {
     dim3 grid(((Ntot + 127) / 128) * ((K + 63) / 64), 1, splits);
     if (variant == 1)
       hipLaunchKernelGGL((wgrad_kernel<64, 128>), grid, dim3(256), 0, st, g);

@@ -582,6 +582,21 @@ _WGRAD_WGS = 768
 # standalone, profiles/r06/bench_wgrad_kg.txt), and the stride-2 / 1x1 wgrads, whose slabs are small and whose kernels
 # ran 2-8 us slower each in the serialized trunk (profiles/r06/trunk_table_serial.txt).
 WGRAD_VARIANT = 8
+# conv.hip's strip kernel (explicit variants 9 / 10 only): all nine taps of a 3x3 / stride-1 / pad-1 conv from one LDS
+# strip of X rows.  A tile spans every tap, so a split is (C / 64) * (K / tile) workgroups; it targets one 12-wave
+# workgroup per CU.  The automatic choice does not pick it: it sums in another fp32 order than the rings, and over the
+# benchmark's 60 Adam steps that rounding grows into parameter differences far beyond rounding (an element whose
+# gradient is at rounding level moves +lr or -lr), so the trunk keeps the rings' bits.
+_WGRAD_STRIP_KB = {9: 64, 10: 32}  # output channels per tile
+_WGRAD_STRIP_WGS = 256
+
+
+def wgrad_strip_split_count(N: int, H: int, splits: int) -> int:
+    """The split count a strip wgrad launch (variants 9, 10) asked for ``splits`` really uses (conv.hip
+    launch_wgrad_strip): whole image rows per split, each image's pad row counted, every split non-empty."""
+    rows = N * (H + 1)
+    per = -(-rows // max(1, int(splits)))
+    return -(-rows // per)
 
 
 def _wgrad_min_pix(out_elems, tiles):
@@ -637,17 +652,25 @@ def conv_wgrad(x, dy, dw, R, S, stride, pad, creal=None, variant=-1, splits=None
         raise ValueError("conv_wgrad shapes")
     P = N * Ho * Wo
     tiles = ((Kc + 127) // 128) * ((R * S * C + 127) // 128)
-    if variant == -1:
+    if variant == -1:  # (never the strip kernel: see above)
         variant = WGRAD_VARIANT if (Kc > 64 and stride == 1 and R * S > 1) else 4
+    strip = variant in _WGRAD_STRIP_KB
     kg = 2 if variant == 8 else 1  # K-groups per workgroup
-    if splits is None:  # ~768 groups of 8 waves (3 per CU), >= _wgrad_min_pix pixels each
-        splits = int(max(1, min(-(-_WGRAD_WGS // (kg * tiles)), P // (kg * _wgrad_min_pix(Kc * R * S * C, tiles)))))
+    if strip:
+        if splits is None:  # one workgroup per CU, >= 1024 padded pixels each
+            stiles = max(1, (C // 64) * (Kc // _WGRAD_STRIP_KB[variant]))
+            splits = max(1, min(_WGRAD_STRIP_WGS // stiles, N * (H + 1) * (W + 1) // 1024))
+        eff = wgrad_strip_split_count(N, H, splits)
+    else:
+        if splits is None:  # ~768 groups of 8 waves (3 per CU), >= _wgrad_min_pix pixels each
+            splits = int(max(1, min(-(-_WGRAD_WGS // (kg * tiles)),
+                                    P // (kg * _wgrad_min_pix(Kc * R * S * C, tiles)))))
+        eff = wgrad_split_count(P, splits)
     ws = torch.empty(splits * Kc * R * S * C, device=x.device, dtype=torch.float32)
     if defer is not None:
         _launch("conv_wgrad", (N, H, W, C, Kc, R, stride), "mer_conv_wgrad_partials", N, H, W, C, Kc, R, S, stride,
                 pad, x.data_ptr(), dy.data_ptr(), int(splits), ws.data_ptr(), int(variant), stream_ptr())
-        defer.add(ws, dw, Kc, C, dw.numel() // Kc if dw_map is not None else creal, R * S,
-                  wgrad_split_count(P, splits), dw_map)
+        defer.add(ws, dw, Kc, C, dw.numel() // Kc if dw_map is not None else creal, R * S, eff, dw_map)
         return
     _launch("conv_wgrad", (N, H, W, C, Kc, R, stride), "mer_conv_wgrad_ex", N, H, W, C, creal, Kc, R, S, stride, pad,
             x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(splits), ws.data_ptr(), int(variant), stream_ptr())

@@ -3,7 +3,8 @@ per launch, the median over workgroups of prologue (address setup + first DMAs),
 and the launch span; stride-2 input gradients per parity class.  Shapes of the B=32 step (256 frames of 112x112).
     python tools/pipe_phases.py build      (here: hipcc, no GPU)
     python tools/pipe_phases.py run [variants, e.g. 2,7,8]   (GPU box)
-    python tools/pipe_phases.py wgrad [variants, e.g. 4,5,8] (GPU box: wgrad_pipe_kernel's K loop, per K-step)"""
+    python tools/pipe_phases.py wgrad [variants, e.g. 4,8,10] [--bound]  (GPU box: the wgrad kernels' K loops, per
+                                           K-step; --bound: beside the no-DMA and no-fragment-read diagnostic forms)"""
 import ctypes
 import sys
 from pathlib import Path
@@ -94,9 +95,11 @@ def run(variants):
                 print(line, flush=True)
 
 
-def run_wgrad(variants):
-    """wgrad_pipe_kernel (same stamp slots): the 3x3 weight gradients of the B=32 step at the step's split counts;
-    K-steps per K-group = the split's 64-pixel steps / groups."""
+def run_wgrad(variants, bound=False):
+    """wgrad_pipe_kernel and wgrad_strip_kernel (same stamp slots): the 3x3 weight gradients of the B=32 step at the
+    step's split counts; K-steps per K-group = the split's 64-pixel steps / groups (strip: 64-slot steps of the padded
+    index).  bound: the K-step time of the real loop beside the two diagnostic forms of the timing build (mer_ct_mode:
+    1 = no LDS-DMA issue after the prologue, 2 = fragment reads of the first K-step only)."""
     import numpy as np
     import torch
     sys.path.insert(0, str(ROOT))
@@ -105,6 +108,7 @@ def run_wgrad(variants):
     from multimodalemotionrecognition_amd import kernels as K
     tick_us = 0.01
     torch.manual_seed(0)
+    dll = _lib.LIB.load()._dll
     for name, H, C, Kc, st in [("layer1 3x3", 28, 64, 64, 1)] + SHAPES:
         Ho = (H + 2 - 3) // st + 1
         P = NF * Ho * Ho
@@ -112,34 +116,52 @@ def run_wgrad(variants):
         dy = (torch.rand(NF, Ho, Ho, Kc, device="cuda") * 2 - 1).bfloat16()
         tiles = ((Kc + 127) // 128) * ((9 * C + 127) // 128)
         for v in variants:
-            kg = 2 if v == 8 else 1
-            splits = int(max(1, min(-(-K._WGRAD_WGS // (kg * tiles)), P // (kg * K._wgrad_min_pix(Kc * 9 * C, tiles)))))
-            steps = -(-(-(-P // splits)) // 64) / kg
+            if v in K._WGRAD_STRIP_KB:
+                if st != 1 or Kc % K._WGRAD_STRIP_KB[v]:
+                    continue
+                stiles = (C // 64) * (Kc // K._WGRAD_STRIP_KB[v])
+                splits = max(1, min(K._WGRAD_STRIP_WGS // stiles, NF * (H + 1) * (H + 1) // 1024))
+                rows = NF * (H + 1)
+                steps = -(-(-(-rows // splits)) * (H + 1) // 64)
+            else:
+                kg = 2 if v == 8 else 1
+                splits = int(max(1, min(-(-K._WGRAD_WGS // (kg * tiles)),
+                                        P // (kg * K._wgrad_min_pix(Kc * 9 * C, tiles)))))
+                steps = -(-(-(-P // splits)) // 64) / kg
             dw = torch.zeros(Kc, C, 3, 3, device="cuda")
             fn = lambda: K.conv_wgrad(x, dy, dw, 3, 3, st, 1, variant=v, splits=splits)  # noqa: E731
-            for _ in range(4):
+            per_step = []
+            for mode in ((0, 1, 2) if bound else (0,)):
+                assert dll.mer_ct_mode(mode) == 0
+                for _ in range(4):
+                    fn()
+                torch.cuda.synchronize()
+                assert dll.mer_ctp_reset() == 0
                 fn()
-            torch.cuda.synchronize()
-            assert _lib.LIB._dll.mer_ctp_reset() == 0
-            fn()
-            torch.cuda.synchronize()
-            t = np.zeros((4096, 8), dtype=np.int64)
-            assert _lib.LIB._dll.mer_ctp_read(ctypes.c_void_p(t.ctypes.data)) == 0
-            tt = t[(t[:, 0] != 0) & (t[:, 4] != 0)].astype(np.float64)
-            if not len(tt):
-                print(f"{name:12s} wgrad v{v}: no stamps")
-                continue
-            ph = [np.median(tt[:, k + 1] - tt[:, k]) * tick_us for k in range(4)]
-            print(f"{name:12s} wgrad v{v}: splits {splits:3d} WGs {len(tt):4d} span "
-                  f"{(tt[:, 4].max() - tt[:, 0].min()) * tick_us:6.2f} | per WG: pro {ph[0]:5.2f} K {ph[1]:6.2f} "
-                  f"xchg {ph[2]:5.2f} store {ph[3]:5.2f} | K-steps {steps:5.1f}: {ph[1] / steps:5.3f} us per step",
-                  flush=True)
+                torch.cuda.synchronize()
+                t = np.zeros((4096, 8), dtype=np.int64)
+                assert dll.mer_ctp_read(ctypes.c_void_p(t.ctypes.data)) == 0
+                tt = t[(t[:, 0] != 0) & (t[:, 4] != 0)].astype(np.float64)
+                if not len(tt):
+                    print(f"{name:12s} wgrad v{v}: no stamps")
+                    continue
+                ph = [np.median(tt[:, k + 1] - tt[:, k]) * tick_us for k in range(4)]
+                per_step.append(ph[1] / steps)
+                print(f"{name:12s} wgrad v{v} mode {mode}: splits {splits:3d} WGs {len(tt):4d} span "
+                      f"{(tt[:, 4].max() - tt[:, 0].min()) * tick_us:6.2f} | per WG: pro {ph[0]:5.2f} K {ph[1]:6.2f} "
+                      f"xchg {ph[2]:5.2f} store {ph[3]:5.2f} | K-steps {steps:5.1f}: {ph[1] / steps:5.3f} us per step",
+                      flush=True)
+            assert dll.mer_ct_mode(0) == 0
+            if bound and len(per_step) == 3:
+                print(f"{name:12s} wgrad v{v} K-step us: real {per_step[0]:5.3f} | no DMA issue {per_step[1]:5.3f} | "
+                      f"fragment reads hoisted {per_step[2]:5.3f}", flush=True)
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "build":
         halo_phases.build()
     elif sys.argv[1] == "wgrad":
-        run_wgrad([int(v) for v in (sys.argv[2] if len(sys.argv) > 2 else "4,5,8").split(",")])
+        args = [a for a in sys.argv[2:] if a != "--bound"]
+        run_wgrad([int(v) for v in (args[0] if args else "4,8,10").split(",")], bound="--bound" in sys.argv)
     else:
         run([int(v) for v in (sys.argv[2] if len(sys.argv) > 2 else "2,7,8").split(",")])

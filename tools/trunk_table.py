@@ -94,7 +94,8 @@ def main():
     bwd = [r for r in win if "conv_pipe_kernel<true" in r["Kernel_Name"].replace(" ", "")
            or "conv_halo_kernel<true" in r["Kernel_Name"].replace(" ", "")
            or "(anonymousnamespace)::wgrad_kernel<" in r["Kernel_Name"].replace(" ", "")
-           or "(anonymousnamespace)::wgrad_pipe_kernel<" in r["Kernel_Name"].replace(" ", "")]
+           or "(anonymousnamespace)::wgrad_pipe_kernel<" in r["Kernel_Name"].replace(" ", "")
+           or "(anonymousnamespace)::wgrad_strip_kernel<" in r["Kernel_Name"].replace(" ", "")]
     dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3  # noqa: E731
     print(f"{'layer':26s} {'pass':6s} {'M x N x K':>22s} {'us':>8s} {'TF/s':>7s} {'attain':>7s} {'frac':>6s}  kernel")
     tot = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}
