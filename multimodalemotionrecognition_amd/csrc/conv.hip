@@ -11,103 +11,18 @@
 // operands are staged [pixel][channel] and read with the gfx950 LDS transpose (ds_read_b64_tr_b16).
 // BatchNorm (train mode: batch statistics, running-stat update with momentum 0.1 / unbiased var)
 // is split into a stats reduction fused into the conv epilogue, a finalize, and an apply pass.
-#include <type_traits>
-
-#include "common.h"
+// This unit holds the forward / input-gradient kernels, the tile plan and their entry points; the weight gradients
+// are in conv_wgrad.hip, the packing kernels in conv_pack.hip, BatchNorm and pooling in bn_pool.hip.
+#include "conv_common.h"
 #include "mer.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-// Phase timestamps of the halo conv (tools/halo_phases.py builds a separate library with -DMER_CONV_TIMING; the
-// production library compiles CT() to nothing): wall_clock64() of workgroup blockIdx.x's thread 0 at slot k.
-#ifdef MER_CONV_TIMING
-static __device__ long long mer_ct_buf[512 * 64];
-#define CT(k) \
-  do { \
-    if (threadIdx.x == 0 && blockIdx.x < 512 && (k) < 64) mer_ct_buf[blockIdx.x * 64 + (k)] = wall_clock64(); \
-  } while (0)
-MER_API int mer_ct_reset() {
-  static long long zeros[512 * 64];
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(mer_ct_buf), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice);
-}
-MER_API int mer_ct_read(long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(mer_ct_buf), sizeof(long long) * 512 * 64, 0, hipMemcpyDeviceToHost);
-}
-// conv_pipe_kernel's phases (tools/pipe_phases.py): slot k of the linear block id (blockIdx.y * gridDim.x + blockIdx.x)
-static __device__ long long mer_ctp_buf[4096 * 8];
-#define CTP(k) \
-  do { \
-    const unsigned b_ = blockIdx.y * gridDim.x + blockIdx.x; \
-    if (threadIdx.x == 0 && b_ < 4096) mer_ctp_buf[b_ * 8 + (k)] = wall_clock64(); \
-  } while (0)
-MER_API int mer_ctp_reset() {
-  static long long zeros[4096 * 8];
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(mer_ctp_buf), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice);
-}
-MER_API int mer_ctp_read(long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(mer_ctp_buf), sizeof(long long) * 4096 * 8, 0, hipMemcpyDeviceToHost);
-}
-// Diagnostic forms of the weight-gradient K loops (tools/pipe_phases.py wgrad --bound; results WRONG): 1 = no LDS-DMA
-// issue after the prologue (what the loop costs without operand fill), 2 = the fragment reads of the first K-step
-// only (what it costs without LDS reads).  The production library compiles CT_MODE() to the constant 0.
-static __device__ int mer_ct_mode_v;
-#define CT_MODE() mer_ct_mode_v
-MER_API int mer_ct_mode(int mode) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(mer_ct_mode_v), &mode, sizeof(int), 0, hipMemcpyHostToDevice);
-}
-#else
-#define CT(k) \
-  do { \
-  } while (0)
-#define CTP(k) \
-  do { \
-  } while (0)
-#define CT_MODE() 0
-#endif
+// timing build: the halo kernel's stamps (CT) and conv_pipe_kernel's (CTP, tools/pipe_phases.py)
+MER_CT_BUFFER(mer_ct, 512 * 64)
+MER_CT_BUFFER(mer_ctp, 4096 * 8)
+#define CT(k) CT_AT(mer_ct_buf, k)
+#define CTP(k) CTP_AT(mer_ctp_buf, k)
 
 namespace {
-
-constexpr int CBK = 64;  // K step
-
-struct ConvGeom {
-  int N, OH, OW;          // GEMM output spatial dims (fwd: Ho,Wo; dgrad: H,W)
-  int IH, IW, IC;         // A-source spatial dims / channels (fwd: H,W,C; dgrad: Ho,Wo,K)
-  int R, S, st, pad;
-  int Ncols;              // GEMM N (fwd: Cout; dgrad: Cin)
-  int Kred;               // R*S*IC
-  const bf16_t* X;        // A source
-  const bf16_t* Wt;       // [Ncols][Kred]
-  bf16_t* Y;              // [M][ldy]
-  long ldy;
-  float* stats;           // fwd: per column (sum, sumsq), may be null
-  const bf16_t* R_;       // residual added in the epilogue (dgrad), may be null
-  const bf16_t* Rmask;    // residual is added only where Rmask > 0 (relu mask), may be null
-  // dgrad only: the BatchNorm-backward reduction of the BN whose relu'd output this gradient flows
-  // into, fused into the epilogue (bn_bwd_reduce semantics; NULL bnr_red = off).  g = (mask > 0) * y,
-  // red[p][c] += (sum g, sum g * (x - mean) * rstd); red2 likewise for a second BN reading the same g
-  // (the downsample branch).  One stored row per output row tile (MER_BN_RED_ROWS), like the forward statistics.
-  const bf16_t* bnr_mask;
-  const bf16_t* bnr_x;
-  const float* bnr_ms;
-  float* bnr_red;
-  const bf16_t* bnr_x2;
-  const float* bnr_ms2;
-  float* bnr_red2;
-  int vec;                // 16-byte epilogue (Ncols, ldy multiples of 8, every operand 16-byte aligned)
-  // stride-2 dgrad only: a 1x1 / stride-2 / pad-0 downsample of the same input fused as an extra K segment of parity
-  // class (0, 0) -- the only class its taps reach: dx[2i, 2j] += sum_k dY2[i, j, k] W2t[c][k] (NULL X2 = off)
-  const bf16_t* X2;       // [N][IH][IW][K2], the downsample branch's output gradient
-  const bf16_t* Wt2;      // [Ncols][K2]
-  int K2;
-};
-
-__host__ __device__ inline bool conv_vec_ok(const ConvGeom& g) {
-  const uintptr_t a = (uintptr_t)g.Y | (uintptr_t)g.R_ | (uintptr_t)g.Rmask | (uintptr_t)g.bnr_mask |
-                      (uintptr_t)g.bnr_x | (uintptr_t)g.bnr_x2 | (uintptr_t)g.stats | (uintptr_t)g.bnr_red |
-                      (uintptr_t)g.bnr_red2;
-  return g.Ncols % 8 == 0 && g.ldy % 8 == 0 && (a & 15) == 0;
-}
 
 template <bool DGRAD>
 __device__ __forceinline__ u32x4 conv_a_chunk(const ConvGeom& g, int n, int oh, int ow, bool rowok, int kk, int tap,
@@ -256,917 +171,6 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvGeom g) {
     }
   }
 }
-
-// ---------------------------------------------------------------------------------------
-// wgrad: dW[k][(r,s,c)] += sum_p dY[p][k] X(p; r,s,c).  Split-K over pixels (grid z): each split
-// stores a coalesced fp32 slab, wgrad_reduce sums them into the PyTorch-layout gradient [Cout][Cin][R][S]
-// (scattered fp32 atomics at stride R*S ran ~17x under the atomic peak: MI355X_MICROARCH 'Global float atomics').
-// LDS images [pixel][channel] (+16 pad); MFMA fragments via ds_read_b64_tr_b16.
-// ---------------------------------------------------------------------------------------
-struct WgradGeom {
-  int N, H, W, C;         // X (input activation, NHWC, C padded)
-  int Ho, Wo, K;          // dY
-  int R, S, st, pad;
-  int Creal;              // real input channels (<= C) of the weight
-  const bf16_t* X;
-  const bf16_t* dY;
-  float* ws;              // [splits][K][R*S*C] fp32 partial slabs
-  int pix_per_split;
-  long ldy;               // dY row stride (elements; K for a conv, a column slice of a wider matrix for a Linear)
-  int flat;               // wgrad_pipe_kernel: 1-D grid of splits x tiles, a split's tiles on one XCD (see there)
-};
-
-template <int BM_, int BN_, int WM = 2, int WN = 2, int PF = 1>
-__global__ __launch_bounds__(64 * WM * WN, 2) void wgrad_kernel(WgradGeom g) {
-  constexpr int NT = 64 * WM * WN;
-  constexpr int LDM = BM_ + 16, LDN = BN_ + 16;
-  constexpr int IT = BM_ / WM / 16, JT = BN_ / WN / 16;
-  constexpr int ACH = BM_ * 64 / 8 / NT, BCH = BN_ * 64 / 8 / NT;  // 16B chunks per thread
-  static_assert(ACH * NT * 8 == BM_ * 64 && BCH * NT * 8 == BN_ * 64, "staging split");
-  __shared__ __attribute__((aligned(16))) bf16_t lds[2][64 * LDM + 64 * LDN];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int Ntot = g.R * g.S * g.C;
-  const int P = g.N * g.Ho * g.Wo;
-  const int wnx = (Ntot + BN_ - 1) / BN_, wny = (g.K + BM_ - 1) / BM_;
-  int wtx, wty;
-  xcd_tile(blockIdx.x, wnx, wnx * wny, wtx, wty);
-  const int m0 = wty * BM_, n0 = wtx * BN_;
-  const int p_beg = blockIdx.z * g.pix_per_split, p_end = min(P, p_beg + g.pix_per_split);
-  const int wm = (w / WN) * (BM_ / WM), wn = (w % WN) * (BN_ / WN);
-  constexpr int ACPR = BM_ / 8, BCPR = BN_ / 8;  // chunks per LDS row
-
-  // PF = 1: one register set, the next K-step's loads in flight during this one's MFMAs, __syncthreads per step.
-  // PF = 2: two register sets, K-steps kt+1 and kt+2 in flight; the per-step barrier is a raw s_barrier after
-  // lgkmcnt(0) (this wave's LDS traffic), so the younger register loads stay in flight across it (a
-  // __syncthreads would drain vmcnt to 0 and leave one step of latency hiding).
-  u32x4 ra[ACH], rb[BCH], ra2[ACH], rb2[BCH];
-  // Per-thread constants: a thread always stages the same 16-byte column chunk, so its (tap, c) and the
-  // row offsets of its chunks are fixed; only the pixel base moves (by 64) per K step.
-  const int a_cc = t % ACPR, a_pr0 = t / ACPR;
-  const int b_cc = t % BCPR, b_pr0 = t / BCPR;
-  const int b_nn = n0 + b_cc * 8;
-  const bool b_colok = b_nn < Ntot;
-  const float inv_C = 1.f / g.C, inv_S = 1.f / g.S, inv_HoWo = 1.f / (g.Ho * g.Wo), inv_Wo = 1.f / g.Wo;
-  const int b_tap = b_colok ? fdiv(b_nn, inv_C) : 0;
-  const int b_c = b_colok ? b_nn - b_tap * g.C : 0;
-  const int b_r = fdiv(b_tap, inv_S), b_s = b_tap - fdiv(b_tap, inv_S) * g.S;
-  const int HoWo = g.Ho * g.Wo;
-  // Branch-free staging: every load is unconditional from a clamped (valid) address, its validity kept in a
-  // bit of `okm`; the zeroing select happens at the LDS store, after this K-step's MFMAs.  (A per-lane
-  // condition around a load compiles to a branch and a wait for that load: the staging loads of a K-step
-  // were serialised on the memory latency.)
-  unsigned okm = 0u, okm2 = 0u;
-  auto gload = [&](u32x4* ra, u32x4* rb, unsigned& okm, int p0) {
-    okm = 0u;
-#pragma unroll
-    for (int i = 0; i < ACH; ++i) {
-      const int p = p0 + a_pr0 + i * (NT / ACPR), k = m0 + a_cc * 8;
-      const bool ok = p < p_end && k < g.K;
-      ra[i] = *reinterpret_cast<const u32x4*>(g.dY + (long)(p < p_end ? p : p_beg) * g.ldy + (k < g.K ? k : 0));
-      okm |= (ok ? 1u : 0u) << i;
-    }
-#pragma unroll
-    for (int i = 0; i < BCH; ++i) {
-      const int p = p0 + b_pr0 + i * (NT / BCPR);
-      const int pc = p < p_end ? p : p_beg;
-      const int n = fdiv(pc, inv_HoWo);
-      const int rem = pc - n * HoWo;
-      const int oh = fdiv(rem, inv_Wo), ow = rem - oh * g.Wo;
-      const int ih = oh * g.st - g.pad + b_r, iw = ow * g.st - g.pad + b_s;
-      const bool ok = p < p_end && b_colok && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
-      const int ihc = ih < 0 ? 0 : (ih >= g.H ? g.H - 1 : ih), iwc = iw < 0 ? 0 : (iw >= g.W ? g.W - 1 : iw);
-      rb[i] = *reinterpret_cast<const u32x4*>(g.X + (((long)n * g.H + ihc) * g.W + iwc) * g.C + b_c);
-      okm |= (ok ? 1u : 0u) << (ACH + i);
-    }
-  };
-  auto lstore = [&](int buf, const u32x4* ra, const u32x4* rb, unsigned okm) {
-    const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < ACH; ++i) {
-      const int ch = t + NT * i;
-      *reinterpret_cast<u32x4*>(&lds[buf][(ch / ACPR) * LDM + (ch % ACPR) * 8]) = ((okm >> i) & 1u) ? ra[i] : z;
-    }
-#pragma unroll
-    for (int i = 0; i < BCH; ++i) {
-      const int ch = t + NT * i;
-      *reinterpret_cast<u32x4*>(&lds[buf][64 * LDM + (ch / BCPR) * LDN + (ch % BCPR) * 8]) =
-          ((okm >> (ACH + i)) & 1u) ? rb[i] : z;
-    }
-  };
-  // transposed fragment: elements j=0..7 = Img[k0 + 8*(lane>>4) + j][c0 + (lane&15)]
-  auto tr_frag = [&](const bf16_t* img, int ld, int k0, int c0) -> bf16x8 {
-    const int q = (lane & 15) >> 2, p4 = (lane & 3) * 4;
-    const int kr = k0 + 8 * (lane >> 4);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (kr + q) * ld + c0 + p4));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (kr + 4 + q) * ld + c0 + p4));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
-
-  f32x4 acc[IT][JT];
-#pragma unroll
-  for (int i = 0; i < IT; ++i)
-#pragma unroll
-    for (int j = 0; j < JT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = (p_end - p_beg + 63) / 64;
-  auto compute = [&](int cur) {
-    const bf16_t* Aimg = &lds[cur][0];
-    const bf16_t* Bimg = &lds[cur][64 * LDM];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 af[IT], bfr[JT];
-#pragma unroll
-      for (int i = 0; i < IT; ++i) af[i] = tr_frag(Aimg, LDM, s * 32, wm + i * 16);
-#pragma unroll
-      for (int j = 0; j < JT; ++j) bfr[j] = tr_frag(Bimg, LDN, s * 32, wn + j * 16);
-#pragma unroll
-      for (int i = 0; i < IT; ++i)
-#pragma unroll
-        for (int j = 0; j < JT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-  };
-  if (PF == 1) {
-    if (nk > 0) {
-      gload(ra, rb, okm, p_beg);
-      lstore(0, ra, rb, okm);
-    }
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      gload(ra, rb, okm, p_beg + (kt + 1 < nk ? kt + 1 : kt) * 64);  // unconditional (the last one re-reads, unused)
-      compute(cur);
-      if (kt + 1 < nk) lstore(cur ^ 1, ra, rb, okm);
-      __syncthreads();
-    }
-  } else {
-    // set 1 (ra, rb) carries the even K-steps, set 2 the odd ones; loads past the end re-read step nk-1, unused
-    auto kstep = [&](int k) { return p_beg + (k < nk ? k : nk - 1) * 64; };
-    if (nk > 0) {
-      gload(ra, rb, okm, p_beg);
-      gload(ra2, rb2, okm2, kstep(1));
-      lstore(0, ra, rb, okm);
-    }
-    lds_barrier();
-    for (int kt = 0; kt < nk; kt += 2) {
-      gload(ra, rb, okm, kstep(kt + 2));  // set 1 was stored into LDS by the previous step
-      compute(0);
-      if (kt + 1 < nk) lstore(1, ra2, rb2, okm2);
-      lds_barrier();
-      if (kt + 1 >= nk) break;
-      gload(ra2, rb2, okm2, kstep(kt + 3));
-      compute(1);
-      if (kt + 2 < nk) lstore(0, ra, rb, okm);
-      lds_barrier();
-    }
-  }
-  // partial tile -> this split's fp32 slab [K][R*S*C] (plain coalesced stores; summed by wgrad_reduce)
-  float* slab = g.ws + (long)blockIdx.z * g.K * Ntot;
-#pragma unroll
-  for (int i = 0; i < IT; ++i)
-#pragma unroll
-    for (int j = 0; j < JT; ++j) {
-      const int nn = n0 + wn + j * 16 + (lane & 15);
-      if (nn >= Ntot) continue;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int k = m0 + wm + i * 16 + (lane >> 4) * 4 + rr;
-        if (k < g.K) slab[(long)k * Ntot + nn] = acc[i][j][rr];
-      }
-    }
-}
-
-// wgrad on a global_load_lds ring (the conv_pipe_kernel structure): no staging registers, STAGES-1 K-steps of
-// 64 pixels in flight across each barrier (counted vmcnt + raw s_barrier).  LDS images [64 pixels][BM | BN]
-// are dense rows of 16-byte chunks, chunk c of row r stored at c ^ wswz(r) (the DMA writes lane-linear, so the
-// XOR is applied to each lane's SOURCE chunk and to the transposed fragment read): the 4 rows one
-// ds_read_b64_tr_b16 lane group reads land on distinct bank groups.  Spatial padding, pixels past the split
-// and channels past K / R*S*C read a 16-byte zero chunk in global memory.  Same partial slabs as wgrad_kernel.
-__device__ __attribute__((aligned(16))) uint32_t mer_conv_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ int wswz(int row, int nchunks) { return ((row & 7) << 1) & (nchunks - 1); }
-
-// ds_read_b64_tr_b16 beside LDS-DMAs in flight.  Through the builtin, hipcc waits vmcnt(0) before the first transposed
-// read after a global_load_lds (it cannot tell the ring slot being read from the one being filled): the K loops below
-// issued the next K-step's DMAs and then drained them before reading the current one -- no K-step of fill ever
-// overlapped compute (the .s of wgrad_pipe_kernel had `s_waitcnt vmcnt(0)` ahead of each K-step's reads; without the
-// per-step DMA issue the layer1 K-step took 0.68 us instead of 1.11, profiles/r08/wgrad_bound.txt).  As inline asm the
-// read carries no memory operand, so the counted vmcnt waits of the loop are the only ones; the compiler then does
-// not count these reads on lgkmcnt either: lds_tr_wait<N>() + frag_ready() before the first use of a fragment.
-__device__ __forceinline__ s16x4 lds_read_tr16(const void* p) {
-  typedef __attribute__((address_space(3))) const char lds_cchar;
-  const uint32_t a = (uint32_t)(uintptr_t)(lds_cchar*)p;
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a) : "memory");
-  return v;
-}
-// at most N LDS reads of this wave still in flight (they return in order)
-template <int N>
-__device__ __forceinline__ void lds_tr_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-// orders every use of f after the volatile asm statements before this one (the wait)
-__device__ __forceinline__ void frag_ready(bf16x8& f) { asm volatile("" : "+v"(f)); }
-
-// KG > 1: in-workgroup split-K over the pixels, as in conv_pipe_kernel: KG groups of WM x WN waves, each with its own
-// ring and a contiguous 1/KG of the split's K-steps; the groups' tiles are summed in LDS in group order before the one
-// slab store.  A KG = 2 launch covers the pixels of two one-group splits with the same waves per CU, so it writes (and
-// the fold re-reads) half the fp32 slabs -- ~0.5 of the ~1 GB per step the trunk's weight gradients moved.
-template <int BM_, int BN_, int WM, int WN, int STAGES, int KS = 64, int KG = 1>
-__global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) void wgrad_pipe_kernel(WgradGeom g) {
-  constexpr int WAVES = WM * WN;  // per K-group
-  constexpr int ACW = BM_ / 8, BCW = BN_ / 8;           // 16-byte chunks per LDS row
-  constexpr int ARI = 64 / ACW, BRI = 64 / BCW;         // rows per glds instruction
-  constexpr int IA = KS / ARI / WAVES, IB = KS / BRI / WAVES;  // glds per wave per K-step of KS pixels
-  static_assert(IA * ARI * WAVES == KS && IB * BRI * WAVES == KS, "the K-step must split into whole glds rows");
-  static_assert(KS % 32 == 0, "MFMA k = 32 pixels");
-  constexpr int IT = BM_ / WM / 16, JT = BN_ / WN / 16;
-  constexpr int BUF = KS * (BM_ + BN_);                 // bf16 elements per ring slot
-  extern __shared__ __attribute__((aligned(16))) bf16_t smem_all[];
-  const int t = threadIdx.x, lane = t & 63, kg = (t >> 6) / WAVES, w = (t >> 6) % WAVES;
-  CTP(0);  // (timing build: tools/pipe_phases.py, slots as in conv_pipe_kernel)
-  bf16_t* const smem = smem_all + kg * STAGES * BUF;  // this K-group's ring
-  const int Ntot = g.R * g.S * g.C;
-  const int P = g.N * g.Ho * g.Wo;
-  const int wnx = (Ntot + BN_ - 1) / BN_, wny = (g.K + BM_ - 1) / BM_;
-  int wtx, wty, zs;
-  if (g.flat) {
-    // Every tile of one split reads the same pixel range (dY rows and, for an R x S conv, R*S shifted windows of X
-    // rows).  Split-major over the bijective XCD chunks (xcd_tile on the flattened (split, tile) index): an XCD runs
-    // whole splits, so their tiles fetch the rows into ITS L2 once.  With the z grid the T tiles of a split went
-    // to T different XCDs (linear dispatch order round-robins XCDs) and each re-fetched the rows from HBM:
-    // layer1's 3x3 wgrad read 244 MB per launch for 51 MB of operands (gpurun_out/pmcstep).
-    int tile;
-    xcd_tile(blockIdx.x, wnx * wny, (int)gridDim.x, tile, zs);
-    wty = tile / wnx;
-    wtx = tile - wty * wnx;
-  } else {
-    xcd_tile(blockIdx.x, wnx, wnx * wny, wtx, wty);
-    zs = blockIdx.z;
-  }
-  const int m0 = wty * BM_, n0 = wtx * BN_;
-  const int p_beg = zs * g.pix_per_split, p_end = min(P, p_beg + g.pix_per_split);
-  const int wm = (w / WN) * (BM_ / WM), wn = (w % WN) * (BN_ / WN);
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(mer_conv_zero16);
-
-  // this K-group's K-steps [kb, kb + nk) of the split's nk_all (every group runs the loop nkg times: workgroup-wide
-  // barriers)
-  const int nk_all = (p_end - p_beg + KS - 1) / KS;
-  const int nkg = (nk_all + KG - 1) / KG, kb = __builtin_amdgcn_readfirstlane(kg * nkg);  // (kg is wave-uniform)
-  const int nk = nk_all - kb < nkg ? (nk_all - kb > 0 ? nk_all - kb : 0) : nkg;
-  const int pk0 = p_beg + kb * KS;
-
-  // Staging walks the pixels incrementally: K-steps are staged strictly in order, pk0 first, and a lane's pixel moves
-  // KS pixels per step.  Per DMA a lane keeps its source pointer (it may lie outside the tensor -- padding taps, pixels
-  // past the split -- and is then only ever an operand of a select against the zero chunk) and, for the X operand, the
-  // output pixel's (oh, ow): KS = (dn, dh, dw) in (image, row, column) steps is split once, so a step is two bounded
-  // carries and one pointer add -- no division and no 64-bit multiply in the loop.
-  const int HoWo = g.Ho * g.Wo;
-  const bf16_t* ap[IA];  // dY: linear in the pixel
-  int arow[IA];
-  bool acok[IA];
-#pragma unroll
-  for (int j = 0; j < IA; ++j) {
-    arow[j] = (w * IA + j) * ARI + lane / ACW;
-    const int acol = m0 + ((lane % ACW) ^ wswz(arow[j], ACW)) * 8;
-    acok[j] = acol < g.K;
-    ap[j] = g.dY + ((long)(pk0 + arow[j]) * g.ldy + acol);
-  }
-  const long a_step = (long)KS * g.ldy;
-  const bf16_t* bp[IB];  // X: the tap's pixel of output pixel (n, oh, ow), channel chunk included
-  int brow[IB], boh[IB], bow[IB], bdr[IB], bds[IB];  // tap offset (dr, ds) = (r - pad, s - pad)
-  bool bcok[IB];
-#pragma unroll
-  for (int j = 0; j < IB; ++j) {
-    brow[j] = (w * IB + j) * BRI + lane / BCW;
-    const int col = n0 + ((lane % BCW) ^ wswz(brow[j], BCW)) * 8;
-    bcok[j] = col < Ntot;
-    const int cc = bcok[j] ? col : 0;
-    const int tap = cc / g.C, c = cc - tap * g.C;
-    const int r = tap / g.S;
-    bdr[j] = r - g.pad;
-    bds[j] = tap - r * g.S - g.pad;
-    const int p = pk0 + brow[j];
-    const int n = p / HoWo, rem = p - n * HoWo;
-    boh[j] = rem / g.Wo;
-    bow[j] = rem - boh[j] * g.Wo;
-    bp[j] = g.X + ((((long)n * g.H + boh[j] * g.st + bdr[j]) * g.W + bow[j] * g.st + bds[j]) * g.C + c);
-  }
-  const int s_dn = KS / HoWo, s_rem = KS - s_dn * HoWo, s_dh = s_rem / g.Wo, s_dw = s_rem - s_dh * g.Wo;
-  const int d_step = ((s_dn * g.H + s_dh * g.st) * g.W + s_dw * g.st) * g.C;  // element deltas: the plain step,
-  const int d_wrap_w = g.st * (g.W - g.Wo) * g.C;                            // ow -= Wo, oh += 1
-  const int d_wrap_h = (g.H - g.Ho * g.st) * g.W * g.C;                      // oh -= Ho, n += 1
-  int p_left = p_end - pk0;  // pixels of the split from the K-step being staged on
-  auto stage = [&](int slot) {
-    bf16_t* la = smem + slot * BUF;
-    bf16_t* lb = la + KS * BM_;
-#pragma unroll
-    for (int j = 0; j < IA; ++j) {
-      glds16(((int)(arow[j] < p_left) & (int)acok[j]) ? ap[j] : zero, la + (w * IA + j) * 512);
-      ap[j] += a_step;
-    }
-#pragma unroll
-    for (int j = 0; j < IB; ++j) {
-      // (all four tests evaluated, one select: no per-lane branch)
-      const int ok = (int)(brow[j] < p_left) & (int)bcok[j] &
-                     (int)((unsigned)(__mul24(boh[j], g.st) + bdr[j]) < (unsigned)g.H) &
-                     (int)((unsigned)(__mul24(bow[j], g.st) + bds[j]) < (unsigned)g.W);
-      glds16(ok ? bp[j] : zero, lb + (w * IB + j) * 512);
-      int d = d_step;
-      bow[j] += s_dw;
-      const bool cw = bow[j] >= g.Wo;
-      bow[j] -= cw ? g.Wo : 0;
-      d += cw ? d_wrap_w : 0;
-      boh[j] += s_dh + (cw ? 1 : 0);
-      const bool ch = boh[j] >= g.Ho;
-      boh[j] -= ch ? g.Ho : 0;
-      d += ch ? d_wrap_h : 0;
-      bp[j] += d;
-    }
-    p_left -= KS;
-  };
-  // transposed fragment from a swizzled image with CW chunks per row: elements j = 0..7 =
-  // Img[k0 + 8*(lane>>4) + j][c0 + (lane&15)]
-  auto tr_frag = [&](const bf16_t* img, int CW, int k0, int c0) -> bf16x8 {
-    const int q = (lane & 15) >> 2, p4 = (lane & 3) * 4;
-    const int kr = k0 + 8 * (lane >> 4);
-    const int lc = (c0 + p4) >> 3, sub = (c0 + p4) & 7;
-    const int r0 = kr + q, r1 = kr + 4 + q;
-    const s16x4 lo = lds_read_tr16(img + r0 * CW * 8 + ((lc ^ wswz(r0, CW)) << 3) + sub);
-    const s16x4 hi = lds_read_tr16(img + r1 * CW * 8 + ((lc ^ wswz(r1, CW)) << 3) + sub);
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
-
-  f32x4 acc[IT][JT];
-#pragma unroll
-  for (int i = 0; i < IT; ++i)
-#pragma unroll
-    for (int j = 0; j < JT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int G = IA + IB;
-#pragma unroll
-  for (int s = 0; s < STAGES - 1; ++s)
-    if (s < nk) stage(s);
-  int wslot = STAGES - 1, rslot = 0;  // ring slots: wrapping counters
-#ifdef MER_CONV_TIMING
-  bf16x8 af_h[KS / 32][IT] = {}, bfr_h[KS / 32][JT] = {};  // CT_MODE() 2: the first K-step's fragments, reused
-#endif
-  CTP(1);
-  for (int kt = 0; kt < nkg; ++kt) {
-    const int left = nk - 1 - kt;
-    const int ahead = left < (STAGES - 2) ? left : (STAGES - 2);
-    wait_tiles_in_flight<G>(ahead);
-    lds_barrier();
-    if (kt + STAGES - 1 < nk && CT_MODE() != 1) stage(wslot);
-    wslot = wslot == STAGES - 1 ? 0 : wslot + 1;
-    const bf16_t* Aimg = smem + rslot * BUF;
-    rslot = rslot == STAGES - 1 ? 0 : rslot + 1;
-    if (KG > 1 && kt >= nk) continue;
-    const bf16_t* Bimg = Aimg + KS * BM_;
-#pragma unroll
-    for (int s = 0; s < KS / 32; ++s) {
-      bf16x8 af[IT], bfr[JT];
-#ifdef MER_CONV_TIMING
-      if (CT_MODE() == 2 && kt > 0) {
-#pragma unroll
-        for (int i = 0; i < IT; ++i) af[i] = af_h[s][i];
-#pragma unroll
-        for (int j = 0; j < JT; ++j) bfr[j] = bfr_h[s][j];
-      } else
-#endif
-      {
-#pragma unroll
-        for (int i = 0; i < IT; ++i) af[i] = tr_frag(Aimg, ACW, s * 32, wm + i * 16);
-#pragma unroll
-        for (int j = 0; j < JT; ++j) bfr[j] = tr_frag(Bimg, BCW, s * 32, wn + j * 16);
-        lds_tr_wait<0>();
-#pragma unroll
-        for (int i = 0; i < IT; ++i) frag_ready(af[i]);
-#pragma unroll
-        for (int j = 0; j < JT; ++j) frag_ready(bfr[j]);
-      }
-#ifdef MER_CONV_TIMING
-      if (kt == 0) {
-#pragma unroll
-        for (int i = 0; i < IT; ++i) af_h[s][i] = af[i];
-#pragma unroll
-        for (int j = 0; j < JT; ++j) bfr_h[s][j] = bfr[j];
-      }
-#endif
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < IT; ++i)
-#pragma unroll
-        for (int j = 0; j < JT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-  }
-  CTP(2);
-  if constexpr (KG > 1) {  // groups 1.. hand their tiles to group 0 through LDS; group 0 sums in group order
-    constexpr int LDR = BN_ + 4;
-    __syncthreads();  // every group's last fragment reads are done before the exchange reuses the rings
-    float* const part = reinterpret_cast<float*>(smem_all);
-    if (kg > 0) {
-      float* mine = part + (kg - 1) * BM_ * LDR;
-#pragma unroll
-      for (int i = 0; i < IT; ++i)
-#pragma unroll
-        for (int j = 0; j < JT; ++j)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr)
-            mine[(wm + i * 16 + (lane >> 4) * 4 + rr) * LDR + wn + j * 16 + (lane & 15)] = acc[i][j][rr];
-    }
-    lds_barrier();
-    if (kg > 0) return;
-#pragma unroll
-    for (int i = 0; i < IT; ++i)
-#pragma unroll
-      for (int j = 0; j < JT; ++j)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-          for (int q = 1; q < KG; ++q)
-            acc[i][j][rr] += part[(q - 1) * BM_ * LDR + (wm + i * 16 + (lane >> 4) * 4 + rr) * LDR + wn + j * 16 +
-                                  (lane & 15)];
-  }
-  CTP(3);
-  float* slab = g.ws + (long)zs * g.K * Ntot;
-#pragma unroll
-  for (int i = 0; i < IT; ++i)
-#pragma unroll
-    for (int j = 0; j < JT; ++j) {
-      const int nn = n0 + wn + j * 16 + (lane & 15);
-      if (nn >= Ntot) continue;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int k = m0 + wm + i * 16 + (lane >> 4) * 4 + rr;
-        if (k < g.K) slab[(long)k * Ntot + nn] = acc[i][j][rr];
-      }
-    }
-  CTP(4);
-}
-
-template <int BM_, int BN_, int WM, int WN, int STAGES, int KS = 64, int KG = 1>
-void launch_wgrad_pipe(const WgradGeom& g0, dim3 grid, hipStream_t st) {
-  const size_t ring = (size_t)KG * STAGES * KS * (BM_ + BN_) * sizeof(bf16_t);
-  const size_t xchg = (size_t)(KG - 1) * BM_ * (BN_ + 4) * sizeof(float);
-  const size_t lds = ring > xchg ? ring : xchg;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pipe_kernel<BM_, BN_, WM, WN, STAGES, KS, KG>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return;
-  // split-major 1-D grid over xcd_tile's XCD chunks: the tiles of one split (same dY rows, same shifted X windows)
-  // share an L2 (DESIGN.md section 4e'': layer1 / stem wgrad fetch 244 -> 67 MB per launch)
-  WgradGeom g = g0;
-  g.flat = 1;
-  const dim3 gr(grid.x * grid.z, 1, 1);
-  hipLaunchKernelGGL((wgrad_pipe_kernel<BM_, BN_, WM, WN, STAGES, KS, KG>), gr, dim3(64 * WM * WN * KG), lds, st, g);
-}
-
-// ---------------------------------------------------------------------------------------
-// Strip weight gradient of a 3x3 / stride-1 / pad-1 conv (variants 9 and 10): all nine taps from ONE LDS strip.
-// wgrad_pipe_kernel tiles the (tap, c) axis over workgroups, so every 64x128 tile DMAs its own dY tile and its own
-// shifted X window each K-step: layer1 filled LDS with ~376 MB per launch for 51 MB of operands, and the nine taps'
-// windows are the same rows shifted by a pixel or an image row.  Here the reduction runs over a PADDED pixel index q:
-// an image is H rows of W + 1 slots (slot W is the pad column -- one row's right pad and the next row's left pad)
-// followed by one pad row, so in q space tap (r, s) is the constant shift (r - 1) * (W + 1) + (s - 1) and every
-// border tap, the corners and the image seams included, lands on a pad slot:
-//   dw[k][(r, s, c)] = sum_q dY[q][k] * X[q + (r - 1) * (W + 1) + (s - 1)][c],  dY = X = 0 at pad slots
-// (pad slots DMA the 16-byte zero chunk: validity is evaluated unconditionally and feeds a select).  The cost is
-// (H + 1)(W + 1) / (H W) more K: 7 % at 28x28, 15 % at 14x14.
-// A workgroup owns a (KB output channels) x (9 taps x 64 input channels) tile of one split.  X rows stream through a
-// ring of `xrows` LDS rows [q][64 channels] addressed by (stream row & (xrows - 1)); a K-step of 64 slots DMAs 64 new
-// X rows and its 64 dY rows ([q][KB], a STAGES-deep ring) and reads rows [64 kt, 64 kt + 64 + 2 (W + 2)) of the X
-// stream, which begins W + 2 rows before the split.  12 waves = (tap row r) x (16-channel quarter): a wave reads its dY
-// fragments once per 32 slots and serves its three taps s = 0..2 from the strip at row base r (W + 1) + s with
-// ds_read_b64_tr_b16 -- per K-step 2 x (KB/16 + 3) fragments for 2 x 3 KB/16 MFMAs.  Rows of 8 (4) 16-byte chunks
-// are XOR-swizzled by row bits 1 and 3 (bit 3): the 8 rows {b..b+3, b+8..b+11} one 32-lane half of a transposed read
-// touches then cover all 64 banks for any row base b.  Splits are ranges of image rows (pad rows included); the
-// slabs are wgrad_pipe_kernel's [split][K][tap * C + c], the grid its split-major XCD order.
-struct StripGeom {
-  int N, H, W, C, K;
-  const bf16_t* X;
-  const bf16_t* dY;
-  float* ws;
-  int ldy;
-  int rows_per_split;  // image rows (pad rows included) per split
-  int xrows;           // rows of the X ring: a power of two >= 64 * (ceil(2 (W + 2) / 64) + STAGES)
-};
-
-__device__ __forceinline__ int sswz(int row, int nchunks) {
-  return nchunks == 8 ? ((row & 2) | ((row >> 1) & 4)) : ((row >> 2) & 2);
-}
-
-// one DMA instruction's lane state: the source of this lane's 16 bytes (row `u` of the operand's stream, at padded
-// slot (n, h, w)), walked 64 slots per issue with two bounded carries as in wgrad_pipe_kernel
-struct StripUnit {
-  const bf16_t* p;
-  int n, h, w, u, lim, stride, wstride, dstep;
-};
-
-template <int KB, int STAGES>
-__global__ __launch_bounds__(768, 3) void wgrad_strip_kernel(StripGeom g) {
-  constexpr int KS = 64, NW = 12;
-  constexpr int ACW = KB / 8;    // 16-byte chunks per dY row
-  constexpr int ARI = 64 / ACW;  // dY rows per DMA instruction
-  constexpr int NDU = KS / ARI;  // dY DMA instructions per K-step (the X chunk takes 8)
-  constexpr int IT = KB / 16;
-  constexpr int ABUF = KS * KB;  // bf16 elements per dY ring slot
-  static_assert(NDU >= NW - 8 && 8 + NDU <= 2 * NW, "8 X + NDU dY instructions over 12 waves, one or two each");
-  static_assert(STAGES >= 2 && STAGES <= 4, "vmcnt waits below cover (STAGES - 2) * 2 <= 4");
-  extern __shared__ __attribute__((aligned(16))) bf16_t smem_all[];
-  bf16_t* const xring = smem_all;
-  bf16_t* const aring = smem_all + g.xrows * 64;
-  const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-  CTP(0);
-  const int Wp = g.W + 1, Hp = g.H + 1, IQ = Hp * Wp, HL = Wp + 1;
-  const int Ntot = 9 * g.C;
-  const int nct = g.C / 64, ntile = nct * (g.K / KB);
-  int tile, zs;
-  xcd_tile(blockIdx.x, ntile, (int)gridDim.x, tile, zs);
-  const int kti = tile / nct, cti = tile - kti * nct;
-  const int k0 = kti * KB, c0 = cti * 64;
-  const int TR = g.N * Hp;
-  const int rb = zs * g.rows_per_split, re = min(TR, rb + g.rows_per_split);
-  const int qb = rb * Wp, qlen = (re - rb) * Wp;
-  const int nk = (qlen + KS - 1) / KS;
-  const int NH = (2 * HL + KS - 1) / KS;  // X chunks a K-step reads beyond its own
-  const int xmask = g.xrows - 1;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(mer_conv_zero16);
-
-  const int s_dn = KS / IQ, s_rem = KS - s_dn * IQ, s_dh = s_rem / Wp, s_dw = s_rem - s_dh * Wp;
-  auto unit_init = [&](bool isx, int ui) -> StripUnit {
-    StripUnit a;
-    int row, chunk;
-    if (isx) {
-      row = ui * 8 + (lane >> 3);
-      chunk = (lane & 7) ^ sswz(row, 8);
-      a.stride = g.C;
-      a.lim = qlen + 2 * HL;
-    } else {
-      row = ui * ARI + lane / ACW;
-      chunk = (lane % ACW) ^ sswz(row, ACW);
-      a.stride = g.ldy;
-      a.lim = qlen;
-    }
-    const int qq = qb + row - (isx ? HL : 0) + IQ;  // >= 0: the first image's halo lies in "image -1"
-    const int n1 = qq / IQ, rem = qq - n1 * IQ;
-    a.n = n1 - 1;
-    a.h = rem / Wp;
-    a.w = rem - a.h * Wp;
-    a.u = row;
-    a.wstride = g.W * a.stride;
-    a.dstep = ((s_dn * g.H + s_dh) * g.W + s_dw) * a.stride;
-    // (outside the tensor at pad slots: then only ever an operand of the select against the zero chunk)
-    a.p = (isx ? g.X + c0 : g.dY + k0) + (((long)a.n * g.H + a.h) * g.W + a.w) * a.stride + chunk * 8;
-    return a;
-  };
-  auto issue = [&](StripUnit& a, bf16_t* dst) {
-    const int ok = (int)(a.u < a.lim) & (int)((unsigned)a.n < (unsigned)g.N) & (int)(a.h < g.H) & (int)(a.w < g.W);
-    glds16(ok ? a.p : zero, dst);
-    a.u += KS;
-    int d = a.dstep;
-    a.w += s_dw;
-    const bool cw = a.w >= Wp;  // w -= W + 1, h += 1
-    a.w -= cw ? Wp : 0;
-    d -= cw ? a.stride : 0;
-    a.h += s_dh + (cw ? 1 : 0);
-    const bool ch = a.h >= Hp;  // h -= H + 1, n += 1
-    a.h -= ch ? Hp : 0;
-    d -= ch ? a.wstride : 0;
-    a.n += s_dn + (ch ? 1 : 0);
-    a.p += d;
-  };
-  // DMA instruction `unit` of a K-step: 0..7 the X chunk's 8-row groups, 8.. the dY rows.  Wave w issues unit w and,
-  // where there is one, unit w + 12 (always dY).
-  const bool s0x = w < 8;
-  const bool has1 = NDU > NW - 8 && w + NW - 8 < NDU;
-  StripUnit u0 = unit_init(s0x, s0x ? w : w - 8);
-  StripUnit u1 = unit_init(false, has1 ? w + NW - 8 : 0);
-  int xw = 0;  // ring row of the next X chunk
-  auto stage_x = [&]() {
-    if (s0x) issue(u0, xring + (xw + w * 8) * 64);
-    xw = (xw + KS) & xmask;
-  };
-  auto stage = [&](int aslot) {  // K-step j: X chunk j + NH and dY chunk j
-    bf16_t* la = aring + aslot * ABUF;
-    stage_x();
-    if (!s0x) issue(u0, la + (w - 8) * 512);
-    if (has1) issue(u1, la + (w + NW - 8) * 512);
-  };
-
-  // fragment addresses (bytes from the ring bases): the dY ones are fixed per ring slot; an X row is
-  // (64 kt + fixed) & xmask, and its swizzle reads row bits 1 and 3 only, so the column part is fixed too
-  const int g4 = lane >> 4, fq = (lane & 15) >> 2, p4 = (lane & 3) * 4;
-  const int tr = w >> 2, cq = w & 3;  // this wave's tap row and channel quarter
-  int aoff[2][2][IT], xrow[3][2][2], xcol[3][2][2];
-#pragma unroll
-  for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-    for (int hi = 0; hi < 2; ++hi) {
-      const int row = ss * 32 + 8 * g4 + 4 * hi + fq;
-#pragma unroll
-      for (int i = 0; i < IT; ++i) {
-        const int col = i * 16 + p4;
-        aoff[ss][hi][i] = (row * KB + ((((col >> 3) ^ sswz(row, ACW))) << 3) + (col & 7)) * 2;
-      }
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const int xr = row + tr * Wp + s;
-        const int col = cq * 16 + p4;
-        xrow[s][ss][hi] = xr * 128;
-        xcol[s][ss][hi] = (((((col >> 3) ^ sswz(xr, 8))) << 3) + (col & 7)) * 2;
-      }
-    }
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto frag = [&](const char* lo_p, const char* hi_p) -> bf16x8 {
-    const s16x4 lo = lds_read_tr16(lo_p);
-    const s16x4 hi = lds_read_tr16(hi_p);
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
-
-  f32x4 acc[3][IT];
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int i = 0; i < IT; ++i) acc[s][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const char* const Xb = reinterpret_cast<const char*>(xring);
-  auto read_frags = [&](int ss, const char* Ab, int xbB, bf16x8* af, bf16x8* bfr) {
-#pragma unroll
-    for (int i = 0; i < IT; ++i) af[i] = frag(Ab + aoff[ss][0][i], Ab + aoff[ss][1][i]);
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-      bfr[s] = frag(Xb + (((xbB + xrow[s][ss][0]) & (g.xrows * 128 - 1)) + xcol[s][ss][0]),
-                    Xb + (((xbB + xrow[s][ss][1]) & (g.xrows * 128 - 1)) + xcol[s][ss][1]));
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  constexpr int NFR = 2 * (IT + 3);  // LDS reads of one fragment set
-  auto frags_ready = [&](bf16x8* af, bf16x8* bfr) {
-#pragma unroll
-    for (int i = 0; i < IT; ++i) frag_ready(af[i]);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) frag_ready(bfr[s]);
-  };
-  auto mfma_all = [&](const bf16x8* af, const bf16x8* bfr) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int i = 0; i < IT; ++i) acc[s][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[s], acc[s][i], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  bf16x8 af0[IT], bf0[3], af1[IT] = {}, bf1[3] = {};
-
-  for (int pc = 0; pc < NH; ++pc) stage_x();  // the X stream's first NH chunks: the halo before the split
-#pragma unroll
-  for (int s = 0; s < STAGES - 1; ++s)
-    if (s < nk) stage(s);
-  int wslot = STAGES - 1, rslot = 0;
-  const int xmaskB = g.xrows * 128 - 1;
-  int xbB = 0;  // byte offset of stream row 64 kt in the X ring
-  const int gw = has1 ? 2 : 1;  // this wave's DMAs per stage
-  CTP(1);
-  for (int kt = 0; kt < nk; ++kt) {
-    const int left = nk - 1 - kt;
-    const int fly = (left < (STAGES - 2) ? left : (STAGES - 2)) * gw;  // own DMAs that may stay in flight
-    if (fly <= 0) wait_vmcnt<0>();
-    else if (fly == 1) wait_vmcnt<1>();
-    else if (fly == 2) wait_vmcnt<2>();
-    else wait_vmcnt<4>();
-    lds_barrier();
-    if (kt + STAGES - 1 < nk && CT_MODE() != 1) stage(wslot);
-    wslot = wslot == STAGES - 1 ? 0 : wslot + 1;
-    const char* Ab = reinterpret_cast<const char*>(aring + rslot * ABUF);
-    rslot = rslot == STAGES - 1 ? 0 : rslot + 1;
-    // two fragment sets, the reads one half-step ahead of the MFMAs: every wave reads right after the barrier, so
-    // without MFMAs to issue meanwhile the LDS time of all 12 waves' reads was exposed in every half-step
-    frags_ready(af1, bf1);  // set 1's reads of K-step kt - 1 retired at the barrier's lgkmcnt(0)
-    if (CT_MODE() != 2 || kt == 0) read_frags(0, Ab, xbB, af0, bf0);
-    mfma_all(af1, bf1);  // half-step 1 of K-step kt - 1 (zeros before the first)
-    if (CT_MODE() != 2 || kt == 0) read_frags(1, Ab, xbB, af1, bf1);
-    lds_tr_wait<NFR>();  // set 0 has landed, set 1 may still be in flight
-    frags_ready(af0, bf0);
-    mfma_all(af0, bf0);
-    xbB = (xbB + KS * 128) & xmaskB;
-  }
-  lds_tr_wait<0>();
-  frags_ready(af1, bf1);
-  mfma_all(af1, bf1);
-  CTP(2);
-  CTP(3);
-  float* slab = g.ws + (long)zs * g.K * Ntot;
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      const int nn = (tr * 3 + s) * g.C + c0 + cq * 16 + (lane & 15);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) slab[(long)(k0 + i * 16 + g4 * 4 + rr) * Ntot + nn] = acc[s][i][rr];
-    }
-  CTP(4);
-}
-
-// launches the strip kernel over `splits` row ranges (in: requested, out: the count used -- every split non-empty);
-// hipErrorInvalidValue where the X ring would not fit (W > 126) or the padded index leaves 31 bits
-template <int KB>
-int launch_wgrad_strip(const WgradGeom& g0, int& splits, hipStream_t st) {
-  constexpr int STAGES = 4;
-  StripGeom g{};
-  g.N = g0.N; g.H = g0.H; g.W = g0.W; g.C = g0.C; g.K = g0.K;
-  g.X = g0.X; g.dY = g0.dY; g.ws = g0.ws; g.ldy = (int)g0.ldy;
-  const int Wp = g.W + 1, Hp = g.H + 1;
-  const long TR = (long)g.N * Hp;
-  if (g0.ldy >= (1 << 24) || (TR + Hp) * Wp >= (1L << 30)) return (int)hipErrorInvalidValue;
-  const int chunks = (2 * (Wp + 1) + 63) / 64 + STAGES;
-  int xc = 1;
-  while (xc < chunks) xc *= 2;
-  if (xc > 8) return (int)hipErrorInvalidValue;
-  g.xrows = xc * 64;
-  if (splits < 1) splits = 1;
-  g.rows_per_split = (int)((TR + splits - 1) / splits);
-  splits = (int)((TR + g.rows_per_split - 1) / g.rows_per_split);
-  const size_t lds = ((size_t)g.xrows * 64 + (size_t)STAGES * 64 * KB) * sizeof(bf16_t);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_strip_kernel<KB, STAGES>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return (int)hipErrorInvalidValue;
-  const int tiles = (g.C / 64) * (g.K / KB);
-  hipLaunchKernelGGL((wgrad_strip_kernel<KB, STAGES>), dim3(splits * tiles), dim3(768), lds, st, g);
-  return (int)hipSuccess;
-}
-
-// slab0[i] = sum_z ws[z][i] over the flat [K][R*S*C] index.  A block owns E = 256/SG consecutive elements
-// and SG split-groups: thread (sg, e) sums splits sg, sg+SG, ... with 4 independent loads in flight (the
-// split count reaches ~100 on the stem / layer1, where one serial chain per element was latency-bound),
-// and the SG partials meet in LDS.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(int K, int C, int Creal, int RS, int splits, int SG,
-                                                           float* __restrict__ ws) {
-  __shared__ float part[256];
-  const int E = 256 / SG, e = threadIdx.x % E, sg = threadIdx.x / E;
-  const long total = (long)K * RS * C;
-  const long idx = (long)blockIdx.x * E + e;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (idx < total) {
-    int z = sg;
-    for (; z + 3 * SG < splits; z += 4 * SG) {
-      a0 += ws[(long)z * total + idx];
-      a1 += ws[(long)(z + SG) * total + idx];
-      a2 += ws[(long)(z + 2 * SG) * total + idx];
-      a3 += ws[(long)(z + 3 * SG) * total + idx];
-    }
-    for (; z < splits; z += SG) a0 += ws[(long)z * total + idx];
-  }
-  part[threadIdx.x] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (sg != 0 || idx >= total) return;
-  float s = 0.f;
-  for (int q = 0; q < SG; ++q) s += part[q * E + e];
-  ws[idx] = s;  // slab 0 (only this block ever reads element idx)
-}
-
-// dw[k][c][r][s] += sum_z ws[z][k][(r*S+s)*C + c] for c < Creal, in split order: one pass replacing the
-// reduce + scatter pair.  Block (channel group of 32, k): each thread sums its (tap, channel) elements over
-// the splits (8 loads in flight, clamped, branch-free) into an LDS [tap][32] tile, written back in the
-// PyTorch order (c, r, s) -- a contiguous run of 32*R*S floats.
-__global__ __launch_bounds__(256) void wgrad_fold_scatter_kernel(int K, int C, int Creal, int RS, int splits,
-                                                                 const float* __restrict__ ws, float* __restrict__ dw) {
-  __shared__ float tile[49 * 32];  // R*S <= 49 (7x7 stem)
-  const int k = blockIdx.y, c0 = blockIdx.x * 32;
-  const long slab = (long)K * RS * C;
-  const float* src = ws + (long)k * RS * C;
-  for (int i = threadIdx.x; i < RS * 32; i += 256) {
-    const int tap = i >> 5, c = c0 + (i & 31);
-    const float* e = src + tap * C + (c < Creal ? c : 0);
-    float s = 0.f;
-    for (int z0 = 0; z0 < splits; z0 += 8) {
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = e[(long)(z0 + q < splits ? z0 + q : splits - 1) * slab];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s += z0 + q < splits ? v[q] : 0.f;
-    }
-    tile[i] = c < Creal ? s : 0.f;
-  }
-  __syncthreads();
-  const int ncl = min(32, Creal - c0);
-  const float inv_RS = 1.f / RS;
-  float* dst = dw + ((long)k * Creal + c0) * RS;
-  for (int i = threadIdx.x; i < ncl * RS; i += 256) {  // i = cl*RS + tap
-    const int cl = fdiv(i, inv_RS), tap = i - cl * RS;
-    dst[i] += tile[tap * 32 + cl];
-  }
-}
-
-// dw[k][c][r][s] += slab0[k][(r*S+s)*C + c] for c < Creal.  Block (channel group of 32, k): reads coalesced
-// along c (one 128-byte segment per tap) into an LDS [tap][32] tile, written back in the PyTorch order
-// (c, r, s) -- a contiguous run of 32*R*S floats.
-__global__ __launch_bounds__(256) void wgrad_scatter_kernel(int C, int Creal, int RS, const float* __restrict__ ws,
-                                                            float* __restrict__ dw) {
-  __shared__ float tile[49 * 32];  // R*S <= 49 (7x7 stem)
-  const int k = blockIdx.y, c0 = blockIdx.x * 32;
-  const float* src = ws + (long)k * RS * C;
-  for (int i = threadIdx.x; i < RS * 32; i += 256) {
-    const int tap = i >> 5, c = c0 + (i & 31);
-    tile[i] = c < Creal ? src[tap * C + c] : 0.f;
-  }
-  __syncthreads();
-  const int ncl = min(32, Creal - c0);
-  const float inv_RS = 1.f / RS;
-  float* dst = dw + ((long)k * Creal + c0) * RS;
-  for (int i = threadIdx.x; i < ncl * RS; i += 256) {  // i = cl*RS + tap
-    const int cl = fdiv(i, inv_RS), tap = i - cl * RS;
-    dst[i] += tile[tap * 32 + cl];
-  }
-}
-
-// Batched fold of deferred split-K partial slabs: every weight gradient of one backward segment in ONE launch
-// instead of one or two per convolution (the folds were ~30 launches of 5-12 us each on the critical stream).
-// Record r: dw_r[k][c][tap] += sum_z ws_r[z][k][tap*C + c] (c < Creal), or with a scatter map
-// dw_r[k][map[j]] for source column j = tap*C + c (-1: dropped) -- the stem's 4x4 space-to-depth form
-// gathered back to 7x7x3.  Threads walk the SOURCE order (coalesced slab reads, the bulk of the bytes): a thread
-// owns 4 consecutive source elements (one 16-byte load per split), a block E = 256/SG threads and SG split-groups
-// (thread (sg, e) sums splits sg, sg+SG, ... in batches of 8 loads issued before their adds, the SG partials meet in
-// LDS in order) -- fixed order, deterministic.  The thread's four read-modify-writes of dw issue their loads
-// together: written as four `+=`, each waited for the previous store (possible aliasing), and the 16-byte form ran
-// 245 us per trunk fold (tools/bench_fold.py) against 157 us for the 4-byte form it replaces; now ~146 us.
-struct FoldRec {
-  const float* ws;
-  float* dw;
-  const int* map;
-  int K, C, Creal, RS, splits, SG, blk0, nblk;
-};
-constexpr int kFoldMaxRecs = 32;
-struct FoldTable {
-  int n;
-  FoldRec r[kFoldMaxRecs];
-};
-
-__global__ __launch_bounds__(256) void wgrad_fold_batch_kernel(FoldTable t) {
-  __shared__ f32x4 part[256];
-  const int v = blockIdx.x;
-  const int ri = table_find(t.n, v, [&](int i) { return t.r[i].blk0; });
-  const FoldRec& R = t.r[ri];
-  const int SG = R.SG, E = 256 / SG, e = threadIdx.x % E, sg = threadIdx.x / E;
-  const long row = (long)R.RS * R.C, total = (long)R.K * row;
-  const int lb = v - R.blk0;
-  const long idx = ((long)lb * E + e) * 4;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 a0 = zero4, a1 = zero4, a2 = zero4, a3 = zero4;
-  const int splits = R.splits;
-  if (idx < total) {
-    const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(R.ws + idx);
-    const long st = total / 4;
-    // this thread's splits z = sg + SG * i, i < n: batches of 8 loads issued before their adds (clamped
-    // addresses, zero-selected), chains a0..a3 by i % 4 -- no serial tail
-    const int n = splits > sg ? (splits - sg + SG - 1) / SG : 0;
-    for (int i0 = 0; i0 < n; i0 += 8) {
-      f32x4 w[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int i = i0 + q < n ? i0 + q : n - 1;
-        w[q] = src[(long)(sg + SG * i) * st];
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (i0 + q < n) {
-          if ((q & 3) == 0) a0 += w[q];
-          else if ((q & 3) == 1) a1 += w[q];
-          else if ((q & 3) == 2) a2 += w[q];
-          else a3 += w[q];
-        }
-    }
-  }
-  part[threadIdx.x] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (sg != 0 || idx >= total) return;
-  f32x4 s4 = zero4;
-  for (int q = 0; q < SG; ++q) s4 += part[q * E + e];
-  const long per_k = R.map ? (long)R.Creal : (long)R.Creal * R.RS;
-  const int k = (int)(idx / row), j0 = (int)(idx - (long)k * row);
-  int o[4];
-  float d[4];
-  float* __restrict__ dwk = R.dw + (long)k * per_k;
-#pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4) {
-    const int j = j0 + c4;
-    if (R.map) {
-      o[c4] = R.map[j];
-    } else {
-      const int tap = j / R.C, c = j - tap * R.C;
-      o[c4] = c < R.Creal ? c * R.RS + tap : -1;
-    }
-  }
-#pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4) d[c4] = dwk[o[c4] >= 0 ? o[c4] : 0];  // the 4 read-modify-writes' loads together
-#pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4)
-    if (o[c4] >= 0) dwk[o[c4]] = d[c4] + s4[c4];
-}
-
 
 // ---------------------------------------------------------------------------------------
 // Pipelined fwd / dgrad implicit GEMM: the im2col A tile and the weight tile are DMA'd straight into
@@ -2184,119 +1188,122 @@ __global__ __launch_bounds__(64 * WM * WN * KG, conv_pipe_wpe(WM * WN * KG, BM_,
   if (g.stats) conv_tile_stats<FM, FN, WM, WN>(g, acc, reinterpret_cast<float*>(smem), w, lane, m0, n0, M, ty);
 }
 
-template <bool DGRAD, bool PAR, int BM_, int BN_, int WM = 2, int WN = 2, int STAGES = 2, int KS = 64, int KG = 1>
-int launch_conv_pipe_t(ConvGeom& g, hipStream_t st) {
-  // PAR: grid.x covers the largest parity class (ph = pw = 0), grid.y = the 4 classes
-  const int Mg = PAR ? g.N * ((g.OH + 1) / 2) * ((g.OW + 1) / 2) : g.N * g.OH * g.OW;
-  const long tiles = (long)((Mg + BM_ - 1) / BM_) * ((g.Ncols + BN_ - 1) / BN_);
-  const size_t ring = (size_t)KG * STAGES * (BM_ + BN_) * KS * sizeof(bf16_t);
-  const size_t kgred = KG > 1 ? (size_t)KG * BM_ * (BN_ + 4) * sizeof(float) : 0;  // the split-K tile exchange
-  const size_t lds = ring > kgred ? ring : kgred;
-  if (KG > 1 && !g.vec) return (int)hipErrorInvalidValue;  // the split-K form has the 16-byte epilogue only
-  // a stride-1 input gradient whose BN-backward target has no second (downsample) branch runs the instantiation
-  // without the x2 terms: 24 fewer VGPRs, which keeps the 8-wave tiles at 2 blocks per CU
-  // every reduction segment a whole number of K-steps long and at most 32 taps (one validity bit each; PAR: the
-  // taps of the largest parity class): the scalar-walk staging (FAST)
-  const bool fast = PAR ? (g.IC % KS == 0 && (!g.X2 || g.K2 % KS == 0) && ((g.R + 1) / 2) * ((g.S + 1) / 2) <= 32)
-                        : (g.IC % KS == 0 && g.R * g.S <= 32 && (!DGRAD || g.st == 1));
-  auto launch = [&](void (*kern)(ConvGeom), unsigned gy) -> int {
+// ---------------------------------------------------------------------------------------
+// The tile plan.  Which kernel a forward / input-gradient convolution runs, on which tile and grid, and how many
+// partial rows (forward BN statistics, the dgrad's BN-backward sums: one row per row tile) that launch writes are
+// resolved ONCE, by conv_plan() below, from the geometry and the requested variant.  The entry points launch from the
+// plan and mer_conv_fwd_rows / mer_conv_dgrad_rows report from it: the trunk does not zero its statistics arenas, so
+// a row count that disagreed with the launch would fold unwritten rows or drop a tile.
+// ---------------------------------------------------------------------------------------
+template <int BM_, int BN_, int WM_ = 2, int WN_ = 2, int STAGES_ = 2, int KS_ = 64, int KG_ = 1>
+struct Tile {
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, STAGES = STAGES_, KS = KS_, KG = KG_;
+};
+
+enum ConvFamily { kConvNone, kConvHalo, kConvReg, kConvPipe };  // conv_halo_kernel / conv_kernel / conv_pipe_kernel
+
+struct ConvPlan {
+  int err;         // what the launch returns instead of launching (hipSuccess: launch)
+  ConvFamily family;
+  int halo;        // kConvHalo: halo_kind (1: layer1, 2: the stem)
+  int variant;     // the resolved variant (-1 / 6 requests included)
+  bool par;        // the stride-2 input gradient's parity-class form (grid_y = 4)
+  int BM, BN, WM, WN, STAGES, KS, KG;
+  bool x2, fast;   // the X2 / FAST instantiation switches of conv_pipe_kernel (x2: of conv_halo_kernel too)
+  size_t lds;      // dynamic LDS bytes of a pipelined launch
+  unsigned grid_x, grid_y;
+  int rows;        // partial rows the launch writes
+};
+
+template <bool DGRAD, bool PAR, class T>
+int launch_conv_pipe_t(ConvGeom& g, const ConvPlan& p, hipStream_t st) {
+  // the tile this walk of the ladder arrived at is the one the plan sized the grid, the LDS and the rows for
+  if (T::BM != p.BM || T::BN != p.BN || T::WM != p.WM || T::WN != p.WN || T::STAGES != p.STAGES || T::KS != p.KS ||
+      T::KG != p.KG)
+    return (int)hipErrorInvalidConfiguration;
+  auto launch = [&](void (*kern)(ConvGeom)) -> int {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
+                            (int)p.lds) != hipSuccess)
       return (int)hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, gy), dim3(64 * WM * WN * KG), lds, st, g);
+    hipLaunchKernelGGL(kern, dim3(p.grid_x, p.grid_y), dim3(64 * T::WM * T::WN * T::KG), p.lds, st, g);
     return (int)hipGetLastError();
   };
   if constexpr (DGRAD && !PAR) {
-    if (!g.bnr_x2)
-      return fast ? launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, false, KG, true>, 1)
-                  : launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, false, KG, false>, 1);
+    if (!p.x2)
+      return p.fast ? launch(&conv_pipe_kernel<DGRAD, PAR, T::BM, T::BN, T::WM, T::WN, T::STAGES, T::KS, false, T::KG,
+                                               true>)
+                    : launch(&conv_pipe_kernel<DGRAD, PAR, T::BM, T::BN, T::WM, T::WN, T::STAGES, T::KS, false, T::KG,
+                                               false>);
   }
-  return fast ? launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, true, KG, true>, PAR ? 4 : 1)
-              : launch(&conv_pipe_kernel<DGRAD, PAR, BM_, BN_, WM, WN, STAGES, KS, true, KG, false>, PAR ? 4 : 1);
+  return p.fast
+             ? launch(&conv_pipe_kernel<DGRAD, PAR, T::BM, T::BN, T::WM, T::WN, T::STAGES, T::KS, true, T::KG, true>)
+             : launch(&conv_pipe_kernel<DGRAD, PAR, T::BM, T::BN, T::WM, T::WN, T::STAGES, T::KS, true, T::KG, false>);
 }
 
+inline int conv_bn(const ConvGeom& g) { return g.Ncols <= 64 ? 64 : 128; }
+// below 384 128-row tiles, 64-row tiles (128-row tiles on the deep layers lose 3.5 % of the step); `par`: the four
+// parity classes' tiles, a class taken as a quarter of the pixels
+inline bool conv_small_m(const ConvGeom& g, bool par) {
+  const long M = (long)g.N * g.OH * g.OW / (par ? 4 : 1);
+  const int bn = conv_bn(g);
+  return ((M + 127) / 128) * ((g.Ncols + bn - 1) / bn) * (par ? 4 : 1) < 384;
+}
+
+// The pipelined tile of a variant: calls f(Tile<...>{}) with the tile as a type and returns what f returns.  The one
+// copy of the rule: conv_plan() records the tile through it, launch_conv_plan() instantiates the kernel through it.
 // variant 1: 4-wave tiles; variant 2 (default): 8-wave tiles -- more waves per CU hide the DMA latency of
 // the 2-deep pipeline (tools/bench_conv.py: 1.1-1.3x on every ResNet layer), cf. gemm_bf16.hip
 // pick_variant; variant 3: 16-wave 256-row tiles on the large-M layers.
-template <bool DGRAD, bool PAR>
-int launch_conv_pipe(ConvGeom& g, hipStream_t st, int variant) {
-  const int M = PAR ? g.N * g.OH * g.OW / 4 : g.N * g.OH * g.OW;
-  const int bn = g.Ncols <= 64 ? 64 : 128;
-  const long tiles128 = (long)((M + 127) / 128) * ((g.Ncols + bn - 1) / bn) * (PAR ? 4 : 1);
-  // below 384 128-row tiles, 64-row tiles (128-row tiles on the deep layers lose 3.5 % of the step)
-  const bool small_m = tiles128 < 384;
+template <bool DGRAD, bool PAR, class F>
+int conv_pipe_tile(const ConvGeom& g, int variant, F&& f) {
+  const int bn = conv_bn(g);
+  const bool small_m = conv_small_m(g, PAR);
   if (variant == 7) {  // in-workgroup split-K (two K-groups) on the 64-row tiles
-    if (bn == 64)
-      return PAR ? launch_conv_pipe_t<DGRAD, PAR, 64, 64, 2, 2, 2, 64, 2>(g, st)
-                 : launch_conv_pipe_t<DGRAD, PAR, 64, 64, 2, 2, 3, 64, 2>(g, st);
-    return PAR ? launch_conv_pipe_t<DGRAD, PAR, 64, 128, 2, 4, 2, 64, 2>(g, st)
-               : launch_conv_pipe_t<DGRAD, PAR, 64, 128, 2, 4, 3, 64, 2>(g, st);
+    if (bn == 64) return PAR ? f(Tile<64, 64, 2, 2, 2, 64, 2>{}) : f(Tile<64, 64, 2, 2, 3, 64, 2>{});
+    return PAR ? f(Tile<64, 128, 2, 4, 2, 64, 2>{}) : f(Tile<64, 128, 2, 4, 3, 64, 2>{});
   }
   if (variant == 3 && !small_m) {  // 256-row tiles (8 / 16 waves) for the large-M layers
     // (the 16-wave dgrad tile needs more than 128 VGPRs and would spill to scratch: 8-wave 256 x 64 tiles instead;
     // tools/check_scratch.py keeps every kernel of the library scratch-free)
     if constexpr (DGRAD) {
-      return launch_conv_pipe_t<DGRAD, PAR, 256, 64, 4, 2>(g, st);
+      return f(Tile<256, 64, 4, 2>{});
     } else {
-      if (bn == 64) return launch_conv_pipe_t<DGRAD, PAR, 256, 64, 4, 2>(g, st);
-      return launch_conv_pipe_t<DGRAD, PAR, 256, 128, 4, 4>(g, st);
+      if (bn == 64) return f(Tile<256, 64, 4, 2>{});
+      return f(Tile<256, 128, 4, 4>{});
     }
   }
   if (variant == 5) {  // 32-wide K-tiles on a 4-deep ring (three K-tiles in flight), 4-wave tiles
-    if (bn == 64)
-      return small_m ? launch_conv_pipe_t<DGRAD, PAR, 64, 64, 2, 2, 4, 32>(g, st)
-                     : launch_conv_pipe_t<DGRAD, PAR, 128, 64, 2, 2, 4, 32>(g, st);
-    return small_m ? launch_conv_pipe_t<DGRAD, PAR, 64, 128, 2, 2, 4, 32>(g, st)
-                   : launch_conv_pipe_t<DGRAD, PAR, 128, 128, 2, 4, 4, 32>(g, st);
+    if (bn == 64) return small_m ? f(Tile<64, 64, 2, 2, 4, 32>{}) : f(Tile<128, 64, 2, 2, 4, 32>{});
+    return small_m ? f(Tile<64, 128, 2, 2, 4, 32>{}) : f(Tile<128, 128, 2, 4, 4, 32>{});
   }
   if (variant == 4) {  // variant-2 tiles on a 3-deep ring (two K-tiles in flight across each barrier)
-    if (bn == 64)
-      return small_m ? launch_conv_pipe_t<DGRAD, PAR, 64, 64, 2, 2, 3>(g, st)
-                     : launch_conv_pipe_t<DGRAD, PAR, 128, 64, 4, 2, 3>(g, st);
-    return small_m ? launch_conv_pipe_t<DGRAD, PAR, 64, 128, 2, 4, 3>(g, st)
-                   : launch_conv_pipe_t<DGRAD, PAR, 128, 128, 2, 4, 3>(g, st);
+    if (bn == 64) return small_m ? f(Tile<64, 64, 2, 2, 3>{}) : f(Tile<128, 64, 4, 2, 3>{});
+    return small_m ? f(Tile<64, 128, 2, 4, 3>{}) : f(Tile<128, 128, 2, 4, 3>{});
   }
   if (variant >= 2) {
     // deep layers (small M, one 64-row tile per CU or fewer): a 3-deep ring keeps two K-tiles in flight
     // (tools/bench_conv.py: layer4 3x3 fwd 54.6 -> 44.8 us, dgrad 55.1 -> 47.1 us; the parity-class dgrad
     // and the large-M layers run best on the 2-deep ring at 2 blocks per CU)
     if (bn == 64)
-      return small_m ? (PAR ? launch_conv_pipe_t<DGRAD, PAR, 64, 64, 2, 2>(g, st)
-                            : launch_conv_pipe_t<DGRAD, PAR, 64, 64, 2, 2, 3>(g, st))
-                     : launch_conv_pipe_t<DGRAD, PAR, 128, 64, 4, 2>(g, st);
+      return small_m ? (PAR ? f(Tile<64, 64, 2, 2>{}) : f(Tile<64, 64, 2, 2, 3>{})) : f(Tile<128, 64, 4, 2>{});
     // (a stride-1 input gradient with a second BN-backward branch -- x2: the block-0 output of layers 2-4 -- used to
     // take the 64 x 128 tile because the 128 x 128 one needed 138 VGPRs; bounded to 128 (conv_pipe_wpe) it runs two
     // blocks per CU without spilling: layer2.1.conv1's dgrad 54.0 -> 39.4 us, profiles/r06/bench_conv_x2.txt)
-    return small_m ? (PAR ? launch_conv_pipe_t<DGRAD, PAR, 64, 128, 2, 4>(g, st)
-                          : launch_conv_pipe_t<DGRAD, PAR, 64, 128, 2, 4, 3>(g, st))
-                   : launch_conv_pipe_t<DGRAD, PAR, 128, 128, 2, 4>(g, st);
+    return small_m ? (PAR ? f(Tile<64, 128, 2, 4>{}) : f(Tile<64, 128, 2, 4, 3>{})) : f(Tile<128, 128, 2, 4>{});
   }
-  if (bn == 64)
-    return small_m ? launch_conv_pipe_t<DGRAD, PAR, 64, 64>(g, st) : launch_conv_pipe_t<DGRAD, PAR, 128, 64>(g, st);
-  return small_m ? launch_conv_pipe_t<DGRAD, PAR, 64, 128>(g, st) : launch_conv_pipe_t<DGRAD, PAR, 128, 128>(g, st);
+  if (bn == 64) return small_m ? f(Tile<64, 64>{}) : f(Tile<128, 64>{});
+  return small_m ? f(Tile<64, 128>{}) : f(Tile<128, 128>{});
 }
 
+// the register-staged kernel (variant 0; input gradients of stride > 2)
 template <bool DGRAD>
-int launch_conv(ConvGeom& g, hipStream_t st) {
-  const int M = g.N * g.OH * g.OW;
-  const int bn = g.Ncols <= 64 ? 64 : 128;
-  const long tiles128 = (long)((M + 127) / 128) * ((g.Ncols + bn - 1) / bn);
-  const bool small_m = tiles128 < 384;  // deep layers (layer3/4): halve BM so the grid fills 256 CUs
-  const int nx = (g.Ncols + bn - 1) / bn;
-  if (bn == 64) {
-    if (small_m) {
-      hipLaunchKernelGGL((conv_kernel<DGRAD, 64, 64>), dim3(nx * ((M + 63) / 64)), dim3(256), 0, st, g);
-    } else {
-      hipLaunchKernelGGL((conv_kernel<DGRAD, 128, 64>), dim3(nx * ((M + 127) / 128)), dim3(256), 0, st, g);
-    }
-  } else {
-    if (small_m) {
-      hipLaunchKernelGGL((conv_kernel<DGRAD, 64, 128>), dim3(nx * ((M + 63) / 64)), dim3(256), 0, st, g);
-    } else {
-      hipLaunchKernelGGL((conv_kernel<DGRAD, 128, 128>), dim3(nx * ((M + 127) / 128)), dim3(256), 0, st, g);
-    }
-  }
-  return (int)hipGetLastError();
+int launch_conv(ConvGeom& g, const ConvPlan& p, hipStream_t st) {
+  auto launch = [&](void (*kern)(ConvGeom)) -> int {
+    hipLaunchKernelGGL(kern, dim3(p.grid_x), dim3(256), 0, st, g);
+    return (int)hipGetLastError();
+  };
+  if (p.BN == 64) return p.BM == 64 ? launch(&conv_kernel<DGRAD, 64, 64>) : launch(&conv_kernel<DGRAD, 128, 64>);
+  return p.BM == 64 ? launch(&conv_kernel<DGRAD, 64, 128>) : launch(&conv_kernel<DGRAD, 128, 128>);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2493,40 +1500,28 @@ int halo_kind(const ConvGeom& g, bool dgrad) {
   return 0;
 }
 
-int cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || v <= 0)
-      return 256;
-    return v;
-  }();
-  return n;
-}
-
 template <bool DGRAD, class GE, int OCC, bool X2 = true>
-int launch_halo_t(ConvGeom& g, hipStream_t st) {
+int launch_halo_t(ConvGeom& g, const ConvPlan& p, hipStream_t st) {
   constexpr int WM = 4, WN = 2;  // 8 waves, 32 x 32 each: conv_pipe_kernel's 128 x 64 tile (variant 2)
   const size_t lds = GE::LDS_ELEMS * sizeof(bf16_t);
   static_assert(GE::LDS_ELEMS * 2 * OCC <= 160 * 1024, "LDS per CU");
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<DGRAD, GE, WM, WN, OCC, X2>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return (int)hipErrorInvalidConfiguration;
-  const int M = g.N * g.OH * g.OW, ntiles = (M + halo::BM - 1) / halo::BM;
-  const int slots = OCC * cu_count();
-  hipLaunchKernelGGL((conv_halo_kernel<DGRAD, GE, WM, WN, OCC, X2>), dim3(ntiles < slots ? ntiles : slots),
-                     dim3(64 * WM * WN), lds, st, g);
+  hipLaunchKernelGGL((conv_halo_kernel<DGRAD, GE, WM, WN, OCC, X2>), dim3(p.grid_x), dim3(64 * WM * WN), lds, st, g);
   return (int)hipGetLastError();
 }
 
+constexpr int halo_occ(int kind) { return kind == 1 ? 1 : 2; }  // workgroups per CU (the stem: 71 KB of LDS each)
+
 template <bool DGRAD>
-int launch_conv_halo(ConvGeom& g, hipStream_t st, int kind) {
+int launch_conv_halo(ConvGeom& g, const ConvPlan& p, hipStream_t st) {
   // (the dgrad without a second fused BN -- every layer1 dgrad of the train step -- drops its registers: the
   // per-workgroup accumulators otherwise spill)
   if constexpr (DGRAD)
-    if (kind == 1 && !g.bnr_x2) return launch_halo_t<DGRAD, HaloL1, 1, false>(g, st);
-  if (kind == 1) return launch_halo_t<DGRAD, HaloL1, 1>(g, st);
-  if constexpr (!DGRAD) return launch_halo_t<false, HaloStem, 2>(g, st);  // 71 KB of LDS: two workgroups per CU
+    if (p.halo == 1 && !p.x2) return launch_halo_t<DGRAD, HaloL1, halo_occ(1), false>(g, p, st);
+  if (p.halo == 1) return launch_halo_t<DGRAD, HaloL1, halo_occ(1)>(g, p, st);
+  if constexpr (!DGRAD) return launch_halo_t<false, HaloStem, halo_occ(2)>(g, p, st);
   return (int)hipErrorInvalidValue;
 }
 
@@ -2545,21 +1540,110 @@ int conv_default_variant(const ConvGeom& g, int fallback) {
   return fallback;
 }
 
-int wgrad_default_variant(int K) {
-  (void)K;
-  return 4;
+template <class F>
+int conv_pipe_tile_of(const ConvGeom& g, bool dgrad, bool par, int variant, F&& f) {
+  if (!dgrad) return conv_pipe_tile<false, false>(g, variant, f);
+  return par ? conv_pipe_tile<true, true>(g, variant, f) : conv_pipe_tile<true, false>(g, variant, f);
 }
 
-bool vec_epilogue_enabled() { return true; }
-
-}  // namespace
-
-MER_API int mer_conv_fwd(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
-                         const void* w_packed, void* y, float* stats, void* stream) {
-  return mer_conv_fwd_ex(N, H, W, C, K, R, S, stride, pad, x, w_packed, y, stats, -1, stream);
+// `variant`: as the entry points take it (-1: the default; 6: the halo kernel or an error).  Default: the halo kernel
+// where it applies (layer1, the stem), else the pipelined tiles -- 64-channel input gradients (layer1, the layer2.0
+// input gradients) on 32-wide K-tiles on a 4-deep ring with 4-wave tiles (5; tools/bench_conv.py --fused: layer1
+// 101 -> 65 us, layer2.0 s2 74 -> 51, downsample 48 -> 31), everything else on the 8-wave 64-wide 2-deep ring (2; the
+// deep ring loses 10-50% there), either replaced by conv_default_variant's choice outside the parity-class form.
+ConvPlan conv_plan(const ConvGeom& g, bool dgrad, int variant) {
+  ConvPlan p{};
+  const long M = (long)g.N * g.OH * g.OW;
+  const long nx = (g.Ncols + conv_bn(g) - 1) / conv_bn(g);
+  p.grid_y = 1;
+  p.x2 = true;
+  if (variant == -1 || variant == 6) {
+    if (const int hk = halo_kind(g, dgrad)) {  // persistent workgroups, one partial row each
+      const long ntiles = (M + halo::BM - 1) / halo::BM, slots = (long)halo_occ(hk) * cu_count();
+      p.family = kConvHalo;
+      p.halo = hk;
+      p.variant = 6;
+      p.BM = halo::BM; p.BN = 64; p.WM = 4; p.WN = 2;
+      p.x2 = !(dgrad && hk == 1 && !g.bnr_x2);
+      p.grid_x = (unsigned)(ntiles < slots ? ntiles : slots);
+      p.rows = (int)p.grid_x;
+      return p;
+    }
+    if (variant == 6) {
+      p.err = (int)hipErrorInvalidValue;
+      return p;
+    }
+    variant = dgrad ? (g.Ncols <= 64 ? 5 : 2) : 2;
+    if (!dgrad || g.st == 1) variant = conv_default_variant(g, variant);
+  }
+  p.variant = variant;
+  if (variant == 0 || (dgrad && g.st > 2)) {
+    p.family = kConvReg;
+    p.BM = conv_small_m(g, false) ? 64 : 128;  // deep layers (layer3/4): halve BM so the grid fills 256 CUs
+    p.BN = conv_bn(g);
+    p.WM = p.WN = 2;
+    p.rows = (int)((M + p.BM - 1) / p.BM);
+    p.grid_x = (unsigned)(nx * p.rows);
+    return p;
+  }
+  p.family = kConvPipe;
+  p.par = dgrad && g.st == 2;
+  conv_pipe_tile_of(g, dgrad, p.par, variant, [&](auto t) {
+    using T = decltype(t);
+    p.BM = T::BM; p.BN = T::BN; p.WM = T::WM; p.WN = T::WN; p.STAGES = T::STAGES; p.KS = T::KS; p.KG = T::KG;
+    return 0;
+  });
+  if (p.KG > 1 && !g.vec) p.err = (int)hipErrorInvalidValue;  // the split-K form has the 16-byte epilogue only
+  const size_t ring = (size_t)p.KG * p.STAGES * (p.BM + p.BN) * p.KS * sizeof(bf16_t);
+  const size_t kgred = p.KG > 1 ? (size_t)p.KG * p.BM * (p.BN + 4) * sizeof(float) : 0;  // the split-K tile exchange
+  p.lds = ring > kgred ? ring : kgred;
+  // a stride-1 input gradient whose BN-backward target has no second (downsample) branch runs the instantiation
+  // without the x2 terms: 24 fewer VGPRs, which keeps the 8-wave tiles at 2 blocks per CU
+  p.x2 = !(dgrad && !p.par && !g.bnr_x2);
+  // every reduction segment a whole number of K-steps long and at most 32 taps (one validity bit each; PAR: the
+  // taps of the largest parity class): the scalar-walk staging (FAST)
+  p.fast = p.par ? (g.IC % p.KS == 0 && (!g.X2 || g.K2 % p.KS == 0) && ((g.R + 1) / 2) * ((g.S + 1) / 2) <= 32)
+                 : (g.IC % p.KS == 0 && g.R * g.S <= 32 && (!dgrad || g.st == 1));
+  const long nbn = (g.Ncols + p.BN - 1) / p.BN;
+  if (!p.par) {
+    p.rows = (int)((M + p.BM - 1) / p.BM);
+    p.grid_x = (unsigned)(p.rows * nbn);
+    return p;
+  }
+  // PAR: grid.x covers the largest parity class (ph = pw = 0), grid.y = the 4 classes; a class's row tiles store their
+  // rows back to back (red_row)
+  p.grid_y = 4;
+  for (int cls = 0; cls < 4; ++cls) {
+    const int ph = cls >> 1, pw = cls & 1;
+    const long Mc = (long)g.N * ((g.OH - ph + 1) >> 1) * ((g.OW - pw + 1) >> 1);
+    p.rows += (int)((Mc + p.BM - 1) / p.BM);
+    if (cls == 0) p.grid_x = (unsigned)((Mc + p.BM - 1) / p.BM * nbn);
+  }
+  return p;
 }
 
-namespace {
+template <bool DGRAD>
+int launch_conv_plan(ConvGeom& g, const ConvPlan& p, hipStream_t st) {
+  if (p.err != (int)hipSuccess) return p.err;
+  if (p.family == kConvHalo) return launch_conv_halo<DGRAD>(g, p, st);
+  if (p.family == kConvReg) return launch_conv<DGRAD>(g, p, st);
+  if constexpr (DGRAD)
+    if (p.par)
+      return conv_pipe_tile<true, true>(g, p.variant,
+                                        [&](auto t) { return launch_conv_pipe_t<true, true, decltype(t)>(g, p, st); });
+  return conv_pipe_tile<DGRAD, false>(g, p.variant,
+                                      [&](auto t) { return launch_conv_pipe_t<DGRAD, false, decltype(t)>(g, p, st); });
+}
+
+// What mer_conv_fwd_rows / mer_conv_dgrad_rows report: the plan's count where the launch is the library's own choice
+// (the halo kernel, the default pipelined tile); for any other request an upper bound -- rows past the tiles stay as
+// the caller left them (zeroed) -- of one row per 64 GEMM rows plus the parity classes' tails (MER_BN_RED_ROWS(M) - 64)
+int conv_plan_rows(const ConvGeom& g, bool dgrad, int variant) {
+  const ConvPlan p = conv_plan(g, dgrad, variant);
+  if (p.family == kConvHalo || (variant == -1 && p.family == kConvPipe)) return p.rows;
+  return (int)(((long)g.N * g.OH * g.OW + 63) / 64 + (dgrad ? 4 : 0));
+}
+
 ConvGeom fwd_geom(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
                   const void* w_packed, void* y, float* stats) {
   ConvGeom g{};
@@ -2568,7 +1652,7 @@ ConvGeom fwd_geom(int N, int H, int W, int C, int K, int R, int S, int stride, i
   g.R = R; g.S = S; g.st = stride; g.pad = pad;
   g.Ncols = K; g.Kred = R * S * C;
   g.X = (const bf16_t*)x; g.Wt = (const bf16_t*)w_packed; g.Y = (bf16_t*)y; g.ldy = K; g.stats = stats;
-  g.vec = vec_epilogue_enabled() && conv_vec_ok(g);
+  g.vec = conv_vec_ok(g);
   return g;
 }
 
@@ -2581,81 +1665,34 @@ ConvGeom dgrad_geom(int N, int H, int W, int C, int K, int R, int S, int stride,
   g.Ncols = C; g.Kred = R * S * K;
   g.X = (const bf16_t*)dy; g.Wt = (const bf16_t*)wt_packed; g.ldy = C; g.stats = nullptr;
   g.X2 = (const bf16_t*)ds_dy;
-  g.vec = vec_epilogue_enabled() && conv_vec_ok(g);
+  g.vec = conv_vec_ok(g);
   return g;
 }
 
-// workgroups of a halo launch (launch_halo_t): one partial row each
-int halo_rows(const ConvGeom& g, int kind) {
-  const long M = (long)g.N * g.OH * g.OW, ntiles = (M + halo::BM - 1) / halo::BM;
-  const long slots = (long)(kind == 1 ? 1 : 2) * cu_count();
-  return (int)(ntiles < slots ? ntiles : slots);
-}
 }  // namespace
+
+MER_API int mer_conv_fwd(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
+                         const void* w_packed, void* y, float* stats, void* stream) {
+  return mer_conv_fwd_ex(N, H, W, C, K, R, S, stride, pad, x, w_packed, y, stats, -1, stream);
+}
 
 MER_API int mer_conv_fwd_rows(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
                               const void* w_packed, int variant) {
   if (N <= 0 || C % 8 || variant < -1 || variant > 7) return -(int)hipErrorInvalidValue;
-  const ConvGeom g = fwd_geom(N, H, W, C, K, R, S, stride, pad, x, w_packed, nullptr, nullptr);
-  if (variant == -1 || variant == 6) {
-    const int hk = halo_kind(g, false);
-    if (hk) return halo_rows(g, hk);
-  }
-  const long M = (long)N * g.OH * g.OW;
-  if (variant == -1) {  // the default pipelined tile: one statistics row per BM-row tile (launch_conv_pipe's choice)
-    const int v = conv_default_variant(g, 2);
-    const int bn = g.Ncols <= 64 ? 64 : 128;
-    const bool small_m = ((M + 127) / 128) * ((g.Ncols + bn - 1) / bn) < 384;
-    const int BM = (v == 7 || small_m) ? 64 : 128;
-    return (int)((M + BM - 1) / BM);
-  }
-  return (int)((M + 63) / 64);  // an upper bound: rows past the tiles stay as the caller left them (zeroed)
+  return conv_plan_rows(fwd_geom(N, H, W, C, K, R, S, stride, pad, x, w_packed, nullptr, nullptr), false, variant);
 }
 
 MER_API int mer_conv_dgrad_rows(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* dy,
                                 const void* wt_packed, const void* ds_dy, int variant) {
   if (N <= 0 || K % 8 || C % 8 || variant < -1 || variant > 7) return -(int)hipErrorInvalidValue;
-  const ConvGeom g = dgrad_geom(N, H, W, C, K, R, S, stride, pad, dy, wt_packed, ds_dy);
-  if (variant == -1 || variant == 6) {
-    const int hk = halo_kind(g, true);
-    if (hk) return halo_rows(g, hk);
-  }
-  if (variant == -1 && (stride == 1 || stride == 2)) {
-    // the default pipelined tile (mer_conv_dgrad_ds's variant resolution, launch_conv_pipe's tile rule): one reduction
-    // row per BM-row tile, per parity class for the stride-2 form (red_row: the classes' tiles back to back) -- exact
-    int v = C <= 64 ? 5 : 2;
-    if (stride == 1) v = conv_default_variant(g, v);
-    const bool par = stride == 2;
-    const long Mq = par ? (long)N * H * W / 4 : (long)N * H * W;
-    const int bn = C <= 64 ? 64 : 128;
-    const bool small_m = ((Mq + 127) / 128) * ((C + bn - 1) / bn) * (par ? 4 : 1) < 384;
-    const int BM = (v == 7 || small_m) ? 64 : 128;
-    if (!par) return (int)(((long)N * H * W + BM - 1) / BM);
-    long rows = 0;
-    for (int cls = 0; cls < 4; ++cls) {
-      const int ph = cls >> 1, pw = cls & 1;
-      const long Mc = (long)N * ((H - ph + 1) >> 1) * ((W - pw + 1) >> 1);
-      rows += (Mc + BM - 1) / BM;
-    }
-    return (int)rows;
-  }
-  return (int)(((long)N * H * W + 63) / 64 + 4);  // MER_BN_RED_ROWS(M) - 64: an upper bound (zero the buffer)
+  return conv_plan_rows(dgrad_geom(N, H, W, C, K, R, S, stride, pad, dy, wt_packed, ds_dy), true, variant);
 }
 
 MER_API int mer_conv_fwd_ex(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
                             const void* w_packed, void* y, float* stats, int variant, void* stream) {
   if (C % 8 || variant < -1 || variant > 7) return (int)hipErrorInvalidValue;
   ConvGeom g = fwd_geom(N, H, W, C, K, R, S, stride, pad, x, w_packed, y, stats);
-  // default: the halo kernel where it applies (layer1), else the 8-wave pipelined tiles; variant 6 = halo or fail
-  // (mer_conv_fwd_rows makes the same choice from the same geometry)
-  if (variant == -1 || variant == 6) {
-    const int hk = halo_kind(g, false);
-    if (hk) return launch_conv_halo<false>(g, (hipStream_t)stream, hk);
-  }
-  if (variant == 6) return (int)hipErrorInvalidValue;
-  if (variant == -1) variant = conv_default_variant(g, 2);
-  if (variant == 0) return launch_conv<false>(g, (hipStream_t)stream);
-  return launch_conv_pipe<false, false>(g, (hipStream_t)stream, variant);
+  return launch_conv_plan<false>(g, conv_plan(g, false, variant), (hipStream_t)stream);
 }
 
 MER_API int mer_conv_dgrad(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* dy,
@@ -2685,16 +1722,12 @@ MER_API int mer_conv_dgrad_ds(int N, int H, int W, int C, int K, int R, int S, i
                               const void* bn_x2, const float* bn_ms2, float* bn_red2, const void* ds_dy,
                               const void* ds_wt_packed, int ds_K, int variant, void* stream) {
   if (K % 8 || C % 8 || variant < -1 || variant > 7) return (int)hipErrorInvalidValue;
-  const bool auto_variant = variant == -1;
-  // 64-channel outputs (layer1, the layer2.0 input gradients): 32-wide K-tiles on a 4-deep ring with 4-wave tiles
-  // (tools/bench_conv.py --fused: layer1 101 -> 65 us, layer2.0 s2 74 -> 51, downsample 48 -> 31); wider outputs
-  // keep the 64-wide 2-deep ring (the deep ring loses 10-50% there).  The layer1 shapes take the halo kernel (6).
-  if (variant == -1) variant = C <= 64 ? 5 : 2;
   // the fused downsample: a 1x1 / stride-2 / pad-0 conv of the same input with ds_K output channels, beside a
   // 3x3 / stride-2 / pad-1 conv (its taps land in parity class (0, 0) only, at pixel (2i, 2j)); K-tile aligned.
-  // Checked AFTER the variant is resolved: only the pipelined kernels (variants 1..5) read the second K segment.
+  // Only the pipelined kernels read the second K segment: not the register-staged variant 0 (the default never
+  // resolves to it; the halo test refuses a second segment itself).
   if (ds_dy && (stride != 2 || R != 3 || S != 3 || pad != 1 || !ds_wt_packed || ds_K <= 0 || ds_K % 64 || K % 64 ||
-                variant < 1))
+                variant == 0))
     return (int)hipErrorInvalidValue;
   if (bn_red && (!bn_mask || !bn_x || !bn_ms || (bn_x2 && (!bn_ms2 || !bn_red2)))) return (int)hipErrorInvalidValue;
   if (bn_red && (variant == 0 || stride > 2)) return (int)hipErrorInvalidValue;  // fused only in the pipelined kernel
@@ -2704,1321 +1737,5 @@ MER_API int mer_conv_dgrad_ds(int N, int H, int W, int C, int K, int R, int S, i
   g.bnr_mask = (const bf16_t*)bn_mask; g.bnr_x = (const bf16_t*)bn_x; g.bnr_ms = bn_ms; g.bnr_red = bn_red;
   g.bnr_x2 = (const bf16_t*)bn_x2; g.bnr_ms2 = bn_ms2; g.bnr_red2 = bn_red2;
   g.Wt2 = (const bf16_t*)ds_wt_packed; g.K2 = ds_dy ? ds_K : 0;
-  // (mer_conv_dgrad_rows makes the same choice from the same geometry)
-  if (auto_variant || variant == 6) {
-    const int hk = halo_kind(g, true);
-    if (hk) return launch_conv_halo<true>(g, (hipStream_t)stream, hk);
-  }
-  if (variant == 6) return (int)hipErrorInvalidValue;
-  if (auto_variant && stride == 1) variant = conv_default_variant(g, variant);
-  if (variant == 0 || stride > 2) return launch_conv<true>(g, (hipStream_t)stream);
-  if (stride == 2) return launch_conv_pipe<true, true>(g, (hipStream_t)stream, variant);
-  return launch_conv_pipe<true, false>(g, (hipStream_t)stream, variant);
-}
-
-MER_API int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
-                           const void* x, const void* dy, float* dw, int splits, float* workspace, void* stream) {
-  return mer_conv_wgrad_ex(N, H, W, C, Creal, K, R, S, stride, pad, x, dy, dw, splits, workspace, -1, stream);
-}
-
-static int conv_wgrad_impl(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
-                           const void* x, const void* dy, long ldy, float* dw, int splits, float* workspace,
-                           int variant, void* stream, bool fold = true) {
-  if (C % 8 || K % 8 || variant < -1 || variant > 10 || R * S > 49) return (int)hipErrorInvalidValue;
-  if (variant == -1) variant = wgrad_default_variant(K);
-  // the strip kernel (9: 64 output channels per tile, 10: 32) takes 3x3 / stride-1 / pad-1 convs on whole 64-channel
-  // chunks only
-  const bool strip = variant == 9 || variant == 10;
-  if (strip && (R != 3 || S != 3 || stride != 1 || pad != 1 || C % 64 || K % (variant == 9 ? 64 : 32) || Creal != C))
-    return (int)hipErrorInvalidValue;
-  WgradGeom g{};
-  g.N = N; g.H = H; g.W = W; g.C = C; g.Creal = Creal;
-  g.Ho = (H + 2 * pad - R) / stride + 1; g.Wo = (W + 2 * pad - S) / stride + 1; g.K = K;
-  g.R = R; g.S = S; g.st = stride; g.pad = pad;
-  g.X = (const bf16_t*)x; g.dY = (const bf16_t*)dy; g.ws = workspace;
-  g.ldy = ldy > 0 ? ldy : K;
-  const int P = N * g.Ho * g.Wo;
-  const int splits_req = splits;
-  if (splits < 1) splits = 1;
-  g.pix_per_split = ((P + splits - 1) / splits + 63) / 64 * 64;
-  splits = (P + g.pix_per_split - 1) / g.pix_per_split;  // every split non-empty (<= requested)
-  const int Ntot = R * S * C;
-  hipStream_t st = (hipStream_t)stream;
-  if (strip) {  // splits are ranges of image rows there: `splits` becomes the count it used
-    splits = splits_req;
-    const int rc = variant == 9 ? launch_wgrad_strip<64>(g, splits, st) : launch_wgrad_strip<32>(g, splits, st);
-    if (rc != (int)hipSuccess) return rc;
-  } else if (K <= 64) {
-    dim3 grid(((Ntot + 127) / 128) * ((K + 63) / 64), 1, splits);
-    if (variant == 1)
-      hipLaunchKernelGGL((wgrad_kernel<64, 128>), grid, dim3(256), 0, st, g);
-    else if (variant == 4)
-      launch_wgrad_pipe<64, 128, 2, 4, 2>(g, grid, st);
-    else if (variant == 8)
-      launch_wgrad_pipe<64, 128, 2, 4, 2, 64, 2>(g, grid, st);
-    else if (variant == 5 || variant == 6)
-      launch_wgrad_pipe<64, 128, 2, 4, 3>(g, grid, st);
-    else if (variant == 3)
-      hipLaunchKernelGGL((wgrad_kernel<64, 128, 2, 4, 2>), grid, dim3(512), 0, st, g);
-    else
-      hipLaunchKernelGGL((wgrad_kernel<64, 128, 2, 4>), grid, dim3(512), 0, st, g);
-  } else {
-    dim3 grid(((Ntot + 127) / 128) * ((K + 127) / 128), 1, splits);
-    if (variant == 1)
-      hipLaunchKernelGGL((wgrad_kernel<128, 128>), grid, dim3(256), 0, st, g);
-    else if (variant == 4)
-      launch_wgrad_pipe<128, 128, 2, 4, 2>(g, grid, st);
-    else if (variant == 8)
-      launch_wgrad_pipe<128, 128, 2, 4, 2, 64, 2>(g, grid, st);
-    else if (variant == 5)
-      launch_wgrad_pipe<128, 128, 2, 4, 3>(g, grid, st);
-    else if (variant == 6)
-      launch_wgrad_pipe<128, 128, 2, 4, 4, 32>(g, grid, st);
-    else if (variant == 7)
-      launch_wgrad_pipe<128, 128, 2, 4, 3, 32>(g, grid, st);
-    else if (variant == 3)
-      hipLaunchKernelGGL((wgrad_kernel<128, 128, 2, 4, 2>), grid, dim3(512), 0, st, g);
-    else
-      hipLaunchKernelGGL((wgrad_kernel<128, 128, 2, 4>), grid, dim3(512), 0, st, g);
-  }
-  if (!fold) MER_LAUNCH_CHECK();  // partial slabs left for mer_wgrad_fold_batch
-  constexpr int fold_max = 16;  // most slabs folded in the single fold+scatter pass
-  if (splits > fold_max) {  // many partial slabs: a wide reduce first (one serial chain per element was latency-bound)
-    const int SG = splits >= 64 ? 16 : 8;
-    const long total = (long)K * R * S * C;
-    const int E = 256 / SG;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + E - 1) / E)), dim3(256), 0, st, K, C, Creal, R * S,
-                       splits, SG, workspace);
-    hipLaunchKernelGGL(wgrad_scatter_kernel, dim3((Creal + 31) / 32, K), dim3(256), 0, st, C, Creal, R * S, workspace,
-                       dw);
-  } else {  // few slabs: fold and scatter in one pass
-    hipLaunchKernelGGL(wgrad_fold_scatter_kernel, dim3((Creal + 31) / 32, K), dim3(256), 0, st, K, C, Creal, R * S,
-                       splits, workspace, dw);
-  }
-  MER_LAUNCH_CHECK();
-}
-
-MER_API int mer_conv_wgrad_ex(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
-                              const void* x, const void* dy, float* dw, int splits, float* workspace, int variant,
-                              void* stream) {
-  return conv_wgrad_impl(N, H, W, C, Creal, K, R, S, stride, pad, x, dy, K, dw, splits, workspace, variant, stream);
-}
-
-MER_API int mer_conv_wgrad_partials(int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
-                                    const void* x, const void* dy, int splits, float* workspace, int variant,
-                                    void* stream) {
-  return conv_wgrad_impl(N, H, W, C, C, K, R, S, stride, pad, x, dy, K, nullptr, splits, workspace, variant, stream,
-                         false);
-}
-
-static int fold_sg_max() { return 8; }  // split groups per block for many-slab records
-
-// rows: n x 8 int64 {ws, dw, map, K, C, Creal (map records: output floats per k), R*S, splits}
-MER_API int mer_wgrad_fold_batch(int n, const long long* rows, void* stream) {
-  if (n < 1 || n > kFoldMaxRecs) return (int)hipErrorInvalidValue;
-  FoldTable t{};
-  t.n = n;
-  int blk = 0;
-  for (int i = 0; i < n; ++i) {
-    const long long* q = rows + 8 * i;
-    FoldRec& r = t.r[i];
-    r.ws = (const float*)q[0]; r.dw = (float*)q[1]; r.map = (const int*)q[2];
-    r.K = (int)q[3]; r.C = (int)q[4]; r.Creal = (int)q[5]; r.RS = (int)q[6]; r.splits = (int)q[7];
-    if (!r.ws || !r.dw || r.K < 1 || r.C < 1 || r.C % 4 || r.RS < 1 || r.splits < 1 || r.Creal < 1 ||
-        (!r.map && r.Creal > r.C) || ((uintptr_t)r.ws & 15))
-      return (int)hipErrorInvalidValue;
-    // SG <= 8: E >= 32 consecutive floats per split group, i.e. whole 128-byte lines (SG 16 read half lines: the
-    // slabs are cold by the time the segment folds, so half-used lines cost HBM bytes)
-    r.SG = r.splits > 48 ? fold_sg_max() : (r.splits > 12 ? 4 : 1);
-    const long total = (long)r.K * r.RS * r.C;
-    r.blk0 = blk;
-    r.nblk = (int)((total + 4 * (256 / r.SG) - 1) / (4 * (256 / r.SG)));
-    blk += r.nblk;
-  }
-  hipLaunchKernelGGL(wgrad_fold_batch_kernel, dim3(blk), dim3(256), 0, (hipStream_t)stream, t);
-  MER_LAUNCH_CHECK();
-}
-
-// Linear weight gradient as a 1x1 convolution over M "pixels": dw[n][k] += sum_m dy[m][n] x[m][k].
-MER_API int mer_linear_wgrad(int M, int N, int K, const void* x, const void* dy, long ldy, float* dw, int splits,
-                             float* workspace, void* stream) {
-  if (ldy < N || ldy % 8) return (int)hipErrorInvalidValue;
-  return conv_wgrad_impl(1, 1, M, K, K, N, 1, 1, 1, 0, x, dy, ldy, dw, splits, workspace, -1, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// Packing kernels
-// ---------------------------------------------------------------------------------------
-// video frames NCHW fp32 -> NHWC bf16 with channels zero-padded to Cp
-// one frame per blockIdx.y; Cp == 8: one 16-byte store per pixel
-__global__ void pack_input_kernel(int C, int HW, const float* __restrict__ x, bf16_t* __restrict__ y) {
-  const int n = blockIdx.y;
-  const float* xn = x + (long)n * C * HW;
-  u32x4* yn = reinterpret_cast<u32x4*>(y + (long)n * HW * 8);
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    u32x4 o = {0u, 0u, 0u, 0u};
-    bf16_t* oh = reinterpret_cast<bf16_t*>(&o);
-    for (int c = 0; c < C; ++c) oh[c] = f2bf(xn[(long)c * HW + p]);
-    yn[p] = o;
-  }
-}
-MER_API int mer_pack_input_nhwc(int N, int C, int H, int W, int Cp, const float* x, void* y, void* stream) {
-  if (Cp != 8 || C > 8) return (int)hipErrorInvalidValue;
-  const int HW = H * W;
-  dim3 grid((HW + 255) / 256 < 64 ? (HW + 255) / 256 : 64, N);
-  hipLaunchKernelGGL(pack_input_kernel, grid, dim3(256), 0, (hipStream_t)stream, C, HW, x, (bf16_t*)y);
-  MER_LAUNCH_CHECK();
-}
-
-// Space-to-depth stem input (ResNet conv1: 7x7, stride 2, pad 3 on C <= 4 channels, H and W even):
-// fp32 NCHW [N][C][H][W] -> bf16 [N][H/2+3][W/2+3][16], pixel (j, i) = 2x2 block (j-2, i-2) of the frame
-// with channel (dy*2 + dx)*C + c (zero for the 2 leading / 1 trailing border rows and columns and for
-// channels >= 4C).  The stride-2 7x7 conv then is a stride-1 4x4 conv with no padding on 16 channels
-// (K = 256 instead of 7*7*8 = 392 for the 8-channel-padded direct form); weights: pack mode 2 below.
-template <int C>  // compile-time channel count: the (dy, dx, c) -> s2d channel map unrolls to fixed registers
-__global__ void pack_input_s2d_kernel(int N, int H, int W, const float* __restrict__ x, bf16_t* __restrict__ y) {
-  const int Hs = H / 2 + 3, Ws = W / 2 + 3;
-  const int total = N * Hs * Ws;  // (< 2^22, checked on the host: 32-bit index math, exact float-reciprocal divides --
-                                  // the 64-bit divisions of a long index were most of this kernel's time)
-  const float inv_Ws = 1.f / Ws, inv_Hs = 1.f / Hs;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < total; p += gridDim.x * blockDim.x) {
-    const int q = fdiv(p, inv_Ws);
-    const int i = p - q * Ws;
-    const int n = fdiv(q, inv_Hs);
-    const int j = q - n * Hs;
-    uint32_t o[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    const int jj = j - 2, ii = i - 2;
-    if (jj >= 0 && jj < H / 2 && ii >= 0 && ii < W / 2) {
-      // the 2x2 block's two rows of each channel as float2 loads (adjacent lanes read adjacent 8-byte pairs: one
-      // coalesced 512-byte run per wave instruction)
-      const float* xn = x + (long)n * C * H * W + (long)(2 * jj) * W + 2 * ii;
-      float v[C][4];  // [c][dydx]
-#pragma unroll
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy) {
-          const float2 q2 = *reinterpret_cast<const float2*>(xn + (long)c * H * W + dy * W);
-          v[c][2 * dy] = q2.x;
-          v[c][2 * dy + 1] = q2.y;
-        }
-#pragma unroll
-      for (int ch = 0; ch < 4 * C; ++ch)
-        o[ch >> 1] |= (uint32_t)f2bf(v[ch % C][ch / C]) << ((ch & 1) * 16);
-    }
-    u32x4* dst = reinterpret_cast<u32x4*>(y + (long)p * 16);
-    dst[0] = u32x4{o[0], o[1], o[2], o[3]};
-    dst[1] = u32x4{o[4], o[5], o[6], o[7]};
-  }
-}
-MER_API int mer_pack_input_s2d(int N, int C, int H, int W, const float* x, void* y, void* stream) {
-  if (C < 1 || C > 4 || (H & 1) || (W & 1) || ((uintptr_t)x & 7)) return (int)hipErrorInvalidValue;
-  const long per_frame = (long)(H / 2 + 3) * (W / 2 + 3);
-  if (N < 0 || per_frame >= (1L << 22)) return (int)hipErrorInvalidValue;
-  // the kernel's fdiv index math holds below 2^22 pixels per launch: larger batches go in frame chunks
-  const int chunk = (int)(((1L << 22) - 1) / per_frame);
-  const hipStream_t st = (hipStream_t)stream;
-  for (int n0 = 0; n0 < N; n0 += chunk) {
-    const int nc = N - n0 < chunk ? N - n0 : chunk;
-    const long total = (long)nc * per_frame;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    const float* xc = x + (long)n0 * C * H * W;
-    bf16_t* yc = (bf16_t*)y + n0 * per_frame * 16;
-    if (C == 3) hipLaunchKernelGGL(pack_input_s2d_kernel<3>, dim3(grid), dim3(256), 0, st, nc, H, W, xc, yc);
-    else if (C == 1) hipLaunchKernelGGL(pack_input_s2d_kernel<1>, dim3(grid), dim3(256), 0, st, nc, H, W, xc, yc);
-    else if (C == 2) hipLaunchKernelGGL(pack_input_s2d_kernel<2>, dim3(grid), dim3(256), 0, st, nc, H, W, xc, yc);
-    else hipLaunchKernelGGL(pack_input_s2d_kernel<4>, dim3(grid), dim3(256), 0, st, nc, H, W, xc, yc);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
-
-// PyTorch conv weight [K][C][R][S] fp32 -> fwd [K][R][S][Cp] (transpose=0) or dgrad [Cp][R][S][Kp] (transpose=1)
-__global__ void pack_w_kernel(int K, int C, int R, int S, int Cp, int transpose, const float* __restrict__ w,
-                              bf16_t* __restrict__ out) {
-  const long total = (long)K * R * S * Cp;
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int k, r, s, c;
-    if (!transpose) {
-      c = e % Cp; long q = e / Cp; s = q % S; q /= S; r = q % R; k = q / R;
-    } else {
-      k = e % K; long q = e / K; s = q % S; q /= S; r = q % R; c = q / R;
-    }
-    out[e] = c < C ? f2bf(w[(((long)k * C + c) * R + r) * S + s]) : (bf16_t)0;
-  }
-}
-MER_API int mer_pack_conv_weight(int K, int C, int R, int S, int Cp, int transpose, const float* w, void* out,
-                                 void* stream) {
-  const long total = (long)K * R * S * Cp;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(pack_w_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, K, C, R, S, Cp, transpose, w,
-                     (bf16_t*)out);
-  MER_LAUNCH_CHECK();
-}
-
-// All of a trunk's weight packs in ONE launch (the per-step re-pack in training is ~40 small layouts
-// whose separate launches cost more than their bytes).  desc: n records of 9 int64 =
-// {w, out, K, C, R, S, Cp, transpose (0, 1, or 2 = space-to-depth stem), first element (unused here)};
-// grid.y = record.  Both layouts go
-// through an LDS tile so global reads AND writes are contiguous runs:
-//   transpose 0: block = one output channel k: w[k][c][rs] (C*RS contiguous floats) -> out[k][rs][c<Cp];
-//   transpose 1: block = (input channel c, 64 output channels k0..): w[k][c][rs] (runs of RS) ->
-//                out[c][rs][k0..k0+63].
-// FLAT: one-dimensional grid over every record's blocks (column 8 = the record's first block): no idle blocks (the
-// 2-D form launches 4,096 blocks per record, most of which only exit -- that dispatch was most of its time)
-template <bool FLAT>
-__global__ __launch_bounds__(256) void pack_w_batched_kernel(const long long* __restrict__ desc, int n) {
-  __shared__ float tile[4608];  // max C*RS (512 * 9) or 64 * RS (RS <= 49 -> 3136)
-  int rec = FLAT ? 0 : (int)blockIdx.y;
-  if (FLAT)
-    for (int i = 1; i < n; ++i)
-      if (desc[i * 9 + 8] <= (long long)blockIdx.x) rec = i;
-  const long long* r = desc + rec * 9;
-  const int bx = FLAT ? (int)(blockIdx.x - r[8]) : (int)blockIdx.x;
-  const float* w = reinterpret_cast<const float*>(r[0]);
-  bf16_t* out = reinterpret_cast<bf16_t*>(r[1]);
-  const int K = (int)r[2], C = (int)r[3], RS = (int)(r[4] * r[5]), Cp = (int)r[6];
-  if (r[7] == 3) {  // transposed pack from the forward bf16 pack: src [K][RS][C] -> out [C][RS][K] (C, K % 64 == 0)
-    // block = (tap, 64-channel tile, 64-output tile): 16-byte loads of 64 k-rows into LDS, 16-byte stores of 64 c-rows
-    const uint16_t* src = reinterpret_cast<const uint16_t*>(r[0]);
-    uint16_t* lds = reinterpret_cast<uint16_t*>(tile);  // [64 k][72] (row pad spreads the column gathers)
-    const int kbn = K >> 6, cbn = C >> 6;
-    const int rs = bx / (kbn * cbn), rem = bx - rs * kbn * cbn, cb = rem / kbn, kb = rem - cb * kbn;
-    if (rs >= RS) return;
-    const int k0 = kb * 64, c0 = cb * 64;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = threadIdx.x + 256 * j, kk = i >> 3, ch = (i & 7) * 8;
-      const uint4 v = *reinterpret_cast<const uint4*>(src + ((long)(k0 + kk) * RS + rs) * C + c0 + ch);
-      *reinterpret_cast<uint4*>(lds + kk * 72 + ch) = v;
-    }
-    __syncthreads();
-    uint16_t* ob = reinterpret_cast<uint16_t*>(out);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = threadIdx.x + 256 * j, cc = i >> 3, kc = (i & 7) * 8;
-      uint32_t pk[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        pk[e] = (uint32_t)lds[(kc + 2 * e) * 72 + cc] | ((uint32_t)lds[(kc + 2 * e + 1) * 72 + cc] << 16);
-      *reinterpret_cast<uint4*>(ob + ((long)(c0 + cc) * RS + rs) * K + k0 + kc) = uint4{pk[0], pk[1], pk[2], pk[3]};
-    }
-    return;
-  }
-  if (r[7] == 2) {  // space-to-depth stem: out[k][ry][rx][ch], tap (r, s) = (2ry+dy-1, 2rx+dx-1), ch = (dy*2+dx)*C + c
-    const int k = bx;
-    const int R = (int)r[4], S = (int)r[5], Ro = (R + 2) / 2, So = (S + 2) / 2;
-    if (k >= K) return;
-    const float* src = w + (long)k * C * RS;
-    for (int i = threadIdx.x; i < C * RS; i += 256) tile[i] = src[i];
-    __syncthreads();
-    bf16_t* dst = out + (long)k * Ro * So * Cp;
-    for (int i = threadIdx.x; i < Ro * So * Cp; i += 256) {
-      const int ch = i % Cp, q = i / Cp, rx = q % So, ry = q / So;
-      const int dydx = ch / C, c = ch - dydx * C;
-      const int rr = 2 * ry + (dydx >> 1) - 1, ss = 2 * rx + (dydx & 1) - 1;
-      const bool ok = dydx < 4 && rr >= 0 && rr < R && ss >= 0 && ss < S;
-      dst[i] = ok ? f2bf(tile[c * RS + rr * S + ss]) : (bf16_t)0;
-    }
-  } else if (!r[7]) {
-    const int k = bx;
-    if (k >= K) return;
-    const float* src = w + (long)k * C * RS;
-    const int n = C * RS;
-    if ((n & 3) == 0 && (((uintptr_t)src) & 15) == 0) {
-      for (int i = threadIdx.x; i < n / 4; i += 256)
-        reinterpret_cast<f32x4*>(tile)[i] = reinterpret_cast<const f32x4*>(src)[i];  // [c][rs]
-    } else {
-      for (int i = threadIdx.x; i < n; i += 256) tile[i] = src[i];
-    }
-    __syncthreads();
-    bf16_t* dst = out + (long)k * RS * Cp;
-    // 8 consecutive channels of one tap per thread, one 16-byte store (Cp % 8 == 0); i / Cp by reciprocal
-    const float inv_Cp = 1.f / Cp;
-    for (int i = threadIdx.x; i < RS * Cp / 8; i += 256) {  // i*8 = rs*Cp + c0
-      const int rs = fdiv(i * 8, inv_Cp), c0 = i * 8 - rs * Cp;
-      uint32_t pk[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = c0 + 2 * e;
-        const uint32_t lo = c < C ? f2bf(tile[c * RS + rs]) : 0u, hi = c + 1 < C ? f2bf(tile[(c + 1) * RS + rs]) : 0u;
-        pk[e] = lo | (hi << 16);
-      }
-      *reinterpret_cast<uint4*>(dst + (long)i * 8) = uint4{pk[0], pk[1], pk[2], pk[3]};
-    }
-  } else {
-    const int kb = (K + 63) / 64;
-    const int c = bx / kb, k0 = (bx - c * kb) * 64;
-    if (c >= Cp) return;
-    const int nk = min(64, K - k0);
-    const float inv_RS = 1.f / RS;
-    for (int i = threadIdx.x; i < nk * RS; i += 256) {  // [kk][rs]
-      const int kk = fdiv(i, inv_RS), rs = i - kk * RS;
-      tile[i] = c < C ? w[((long)(k0 + kk) * C + c) * RS + rs] : 0.f;
-    }
-    __syncthreads();
-    bf16_t* dst = out + (long)c * RS * K + k0;
-    if (nk == 64 && (K & 7) == 0) {  // 8 consecutive output channels per thread, one 16-byte store
-      for (int i = threadIdx.x; i < RS * 8; i += 256) {  // i = rs*8 + kk0/8
-        const int rs = i >> 3, kk0 = (i & 7) * 8;
-        uint32_t pk[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          pk[e] = (uint32_t)f2bf(tile[(kk0 + 2 * e) * RS + rs]) | ((uint32_t)f2bf(tile[(kk0 + 2 * e + 1) * RS + rs]) << 16);
-        *reinterpret_cast<uint4*>(dst + (long)rs * K + kk0) = uint4{pk[0], pk[1], pk[2], pk[3]};
-      }
-    } else {
-      for (int i = threadIdx.x; i < RS * nk; i += 256) {  // i = rs*nk + kk
-        const int rs = i / nk, kk = i - rs * nk;
-        dst[(long)rs * K + kk] = f2bf(tile[kk * RS + rs]);
-      }
-    }
-  }
-}
-MER_API int mer_pack_conv_weights(int n, const long long* desc, long total, void* stream) {
-  (void)total;
-  if (n <= 0 || n > 64) return (int)hipErrorInvalidValue;
-  // grid.x covers the largest record: 512 output channels (layout 0) or 512 x 8 (c, k-block) tiles
-  hipLaunchKernelGGL(pack_w_batched_kernel<false>, dim3(512 * 8, n), dim3(256), 0, (hipStream_t)stream, desc, n);
-  MER_LAUNCH_CHECK();
-}
-MER_API int mer_pack_conv_weights_flat(int n, const long long* desc, long total_blocks, void* stream) {
-  if (n <= 0 || n > 64 || total_blocks <= 0 || total_blocks > (1L << 30)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(pack_w_batched_kernel<true>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, desc,
-                     n);
-  MER_LAUNCH_CHECK();
-}
-
-// ---------------------------------------------------------------------------------------
-// BatchNorm2d (train mode), channel-last.  stats[c] = (sum, sumsq) over M = N*H*W values.
-// finalize: ms[c] = (mean, rstd); running_mean = (1-mom) rm + mom*mean; running_var uses the
-// unbiased variance (torch semantics); num_batches_tracked += 1.
-// ---------------------------------------------------------------------------------------
-// Forward statistics layout (mer.h MER_BN_STAT_ROWS): one row per output row tile of the conv (<= ceil(M/64)
-// rows, unused rows zero) followed by 64 scratch rows.  Rows are summed in a fixed order: stage 1 (when
-// there are more than 64 rows) folds contiguous row groups into the 64 scratch rows, stage 2 folds <= 64
-// rows per channel -- deterministic whatever the tile size and block schedule were.
-// Latency: a block here is a short chain (one wave-row of loads, a sum, an LDS meet), so every load of a
-// thread's rows is issued before the first add (batches of 16 from clamped addresses, zero-selected) -- the
-// loop that added as it loaded waited one memory latency per two rows.  The sum order is unchanged: a0 takes
-// the thread's rows 0, 2, 4, ... and a1 rows 1, 3, 5, ... (rows r0 + pg + 4 i).
-__global__ __launch_bounds__(256) void bn_stat_rows_fold_kernel(int C2, int rows, int per, const float* __restrict__ in,
-                                                                float* __restrict__ out) {
-  __shared__ float part[4][64];
-  const int el = threadIdx.x & 63, pg = threadIdx.x >> 6;
-  const int e = blockIdx.x * 64 + el, grp = blockIdx.y;
-  const int r0 = grp * per, r1 = min(rows, r0 + per);
-  const int ec = e < C2 ? e : C2 - 1;
-  const int n = r1 - (r0 + pg) > 0 ? (r1 - (r0 + pg) + 3) / 4 : 0;  // this thread's rows
-  float a0 = 0.f, a1 = 0.f;
-  for (int i0 = 0; i0 < n; i0 += 16) {
-    float x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int r = r0 + pg + 4 * (i0 + i);
-      x[i] = in[(long)(r < r1 ? r : r1 - 1) * C2 + ec];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-      if (i0 + i < n) a0 += x[i];
-      if (i0 + i + 1 < n) a1 += x[i + 1];
-    }
-  }
-  part[pg][el] = a0 + a1;
-  __syncthreads();
-  if (pg == 0 && e < C2) out[(long)grp * C2 + e] = (part[0][el] + part[1][el]) + (part[2][el] + part[3][el]);
-}
-
-// 64 channels per block; the 4 waves split the (<= 64) rows, then meet in LDS
-__global__ __launch_bounds__(256) void bn_finalize_kernel(int C, long M, int rows, const float* __restrict__ stats,
-                                                          float eps, float momentum, float* __restrict__ ms,
-                                                          float* __restrict__ rmean, float* __restrict__ rvar,
-                                                          long long* __restrict__ nbt) {
-  __shared__ float part[4][64][2];
-  const int cl = threadIdx.x & 63, pg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  if (!stats) {  // eval mode: normalise with the running statistics, no update
-    if (pg == 0 && c < C) {
-      ms[2 * c] = rmean[c];
-      ms[2 * c + 1] = rsqrtf(rvar[c] + eps);
-    }
-    return;
-  }
-  float sum = 0.f, sq = 0.f;
-  {  // rows <= 64: this wave's <= 16 rows all in flight before the first add (same order)
-    const int cc = c < C ? c : C - 1;
-    float xs[16], xq[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int p = pg + 4 * i, pc = p < rows ? p : rows - 1;
-      xs[i] = stats[(long)pc * 2 * C + 2 * cc];
-      xq[i] = stats[(long)pc * 2 * C + 2 * cc + 1];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (pg + 4 * i < rows) {
-        sum += xs[i];
-        sq += xq[i];
-      }
-  }
-  part[pg][cl][0] = sum;
-  part[pg][cl][1] = sq;
-  __syncthreads();
-  if (pg != 0 || c >= C) return;
-  sum = part[0][cl][0] + part[1][cl][0] + part[2][cl][0] + part[3][cl][0];
-  sq = part[0][cl][1] + part[1][cl][1] + part[2][cl][1] + part[3][cl][1];
-  const float mean = sum / M;
-  const float var = fmaxf(sq / M - mean * mean, 0.f);
-  ms[2 * c] = mean;
-  ms[2 * c + 1] = rsqrtf(var + eps);
-  if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-  if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * ((float)M / (float)(M > 1 ? M - 1 : 1));
-  if (nbt && c == 0) *nbt += 1;
-}
-// 64 < rows <= BN_WIDE_ROWS: the fold and the finalize in ONE launch (round 6).  16 waves per block; wave w sums rows
-// w, w + 16, ... of the block's 64 columns (lane = column), the 16 wave partials meet in LDS and wave 0 adds them in a
-// fixed pairwise order -- deterministic, like the two-stage form it replaces for ResNet18 layer2 / layer3 (784 / 196
-// rows at B = 32), one ~5 us launch less per BatchNorm.  Every load of a thread's rows (NB <= 64 of them) is issued
-// before the first add: the batches-of-16 loop waited one memory latency per batch, 4 per pass at 784 rows, and the
-// finalize ran its sums and its sums of squares as two such passes (13.4 us per launch in the step trace).  The
-// forward finalize's columns are the interleaved (sum, sumsq) pairs of 32 channels, so one pass carries both and the
-// grid has twice the blocks.  The per-element order (even-ordinal rows into a0, odd into a1, then the wave tree) is
-// the batched loop's, so the results are bitwise those of the round-6 kernels.
-constexpr int BN_WIDE_ROWS = 1024;
-
-template <int N>
-__device__ __forceinline__ float pair_tree(const float* v, int stride) {
-  if constexpr (N == 1) {
-    return v[0];
-  } else {
-    return pair_tree<N / 2>(v, stride) + pair_tree<N / 2>(v + (N / 2) * stride, stride);
-  }
-}
-
-// per-(wave, element) partial over rows w, w + 16, ... (< rows <= 16 * NB): x[r * ld + e]
-// (32-bit offsets from the column's base: rows * ld < 2^31 for every caller, and 64 loads in flight fit in 128 VGPRs)
-template <int NB>
-__device__ __forceinline__ float wide_rows_sum(const float* __restrict__ x, int rows, int ld, int e, int w) {
-  float v[NB];
-  const float* __restrict__ xe = x + e;
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int r = w + 16 * i;
-    v[i] = xe[(r < rows ? r : rows - 1) * ld];
-  }
-  float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-  for (int i = 0; i < NB; i += 2) {
-    if (w + 16 * i < rows) a0 += v[i];
-    if (w + 16 * (i + 1) < rows) a1 += v[i + 1];
-  }
-  return a0 + a1;
-}
-
-template <int NB>
-__device__ __forceinline__ void bn_finalize_wide_body(int C, long M, int rows, const float* __restrict__ stats,
-                                                      float eps, float momentum, float* __restrict__ ms,
-                                                      float* __restrict__ rmean, float* __restrict__ rvar,
-                                                      long long* __restrict__ nbt, float (*part)[64]) {
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + l;  // column of the [rows][C][2] layout: channel col / 2, sum (even) / sumsq (odd)
-  if (blockIdx.x * 64 >= 2 * C) return;  // (block-uniform: the paired launch's grid covers the wider record)
-  part[w][l] = wide_rows_sum<NB>(stats, rows, 2 * C, col < 2 * C ? col : 2 * C - 1, w);
-  __syncthreads();
-  if (w != 0) return;
-  const float tot = pair_tree<16>(&part[0][l], 64);
-  const float sq = __shfl_xor(tot, 1, 64);
-  const int c = col >> 1;
-  if ((l & 1) || c >= C) return;
-  const float sum = tot;
-  const float mean = sum / M;
-  const float var = fmaxf(sq / M - mean * mean, 0.f);
-  ms[2 * c] = mean;
-  ms[2 * c + 1] = rsqrtf(var + eps);
-  if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-  if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * ((float)M / (float)(M > 1 ? M - 1 : 1));
-  if (nbt && c == 0) *nbt += 1;
-}
-
-template <int NB>
-__global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(int C, long M, int rows, const float* __restrict__ stats,
-                                                                float eps, float momentum, float* __restrict__ ms,
-                                                                float* __restrict__ rmean, float* __restrict__ rvar,
-                                                                long long* __restrict__ nbt) {
-  __shared__ float part[16][64];
-  bn_finalize_wide_body<NB>(C, M, rows, stats, eps, momentum, ms, rmean, rvar, nbt, part);
-}
-
-// Two BatchNorms' finalizes in one launch (blockIdx.y = record): a stride-2 BasicBlock's bn2 and downsample BN, whose
-// convs both end before either BatchNorm is applied -- one ~4-7 us launch less on the trunk stream per such block.
-struct BnFinRec {
-  int C, rows;
-  long M;
-  const float* stats;
-  float *ms, *rmean, *rvar;
-  long long* nbt;
-};
-struct BnFinPair {
-  BnFinRec r[2];
-};
-template <int NB>
-__global__ __launch_bounds__(1024) void bn_finalize_wide2_kernel(BnFinPair t, float eps, float momentum) {
-  __shared__ float part[16][64];
-  const bool y = blockIdx.y != 0;  // (uniform selects: an indexed kernel-argument record cost scratch at NB = 64)
-  bn_finalize_wide_body<NB>(y ? t.r[1].C : t.r[0].C, y ? t.r[1].M : t.r[0].M, y ? t.r[1].rows : t.r[0].rows,
-                            y ? t.r[1].stats : t.r[0].stats, eps, momentum, y ? t.r[1].ms : t.r[0].ms,
-                            y ? t.r[1].rmean : t.r[0].rmean, y ? t.r[1].rvar : t.r[0].rvar,
-                            y ? t.r[1].nbt : t.r[0].nbt, part);
-}
-
-// out[e] = sum over parts rows of in[p][e], e < 2C, for 64 < parts <= BN_WIDE_ROWS (one launch; see above)
-template <int NB>
-__global__ __launch_bounds__(1024) void partials_sum_wide_kernel(int C2, int parts, const float* __restrict__ in,
-                                                                 float* __restrict__ out) {
-  __shared__ float part[16][64];
-  const int el = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int e = blockIdx.x * 64 + el, ec = e < C2 ? e : C2 - 1;
-  part[w][el] = wide_rows_sum<NB>(in, parts, C2, ec, w);
-  __syncthreads();
-  if (w == 0 && e < C2) out[e] = pair_tree<16>(&part[0][el], 64);
-}
-// two buffers of the same shape in one launch (blockIdx.y): a stride-2 block's bn2 and downsample-BN backward sums,
-// which one fused dgrad epilogue produced
-template <int NB>
-__global__ __launch_bounds__(1024) void partials_sum_wide2_kernel(int C2, int parts, const float* __restrict__ in0,
-                                                                  float* __restrict__ out0,
-                                                                  const float* __restrict__ in1,
-                                                                  float* __restrict__ out1) {
-  __shared__ float part[16][64];
-  const float* in = blockIdx.y ? in1 : in0;
-  float* out = blockIdx.y ? out1 : out0;
-  const int el = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int e = blockIdx.x * 64 + el, ec = e < C2 ? e : C2 - 1;
-  part[w][el] = wide_rows_sum<NB>(in, parts, C2, ec, w);
-  __syncthreads();
-  if (w == 0 && e < C2) out[e] = pair_tree<16>(&part[0][el], 64);
-}
-
-// the wide launches by row count: NB = 16 / 32 / 64 loads per thread
-template <class F16, class F32, class F64>
-static inline void wide_pick(int rows, F16 f16, F32 f32, F64 f64) {
-  if (rows <= 256) f16();
-  else if (rows <= 512) f32();
-  else f64();
-}
-
-MER_API int mer_bn_finalize(int C, long M, const float* stats, float eps, float momentum, float* ms, float* rmean,
-                            float* rvar, long long* num_batches_tracked, void* stream) {
-  return mer_bn_finalize_rows(C, M, (int)((M + 63) / 64), stats, eps, momentum, ms, rmean, rvar, num_batches_tracked,
-                              stream);
-}
-
-MER_API int mer_bn_finalize_rows2(int C, long M, int data_rows, const float* stats, float* ms, float* rmean, float* rvar,
-                                  long long* nbt, int C2, long M2, int data_rows2, const float* stats2, float* ms2,
-                                  float* rmean2, float* rvar2, long long* nbt2, float eps, float momentum,
-                                  void* stream) {
-  if (!stats || !stats2 || C <= 0 || C2 <= 0 || data_rows <= 0 || data_rows > (M + 63) / 64 || data_rows2 <= 0 ||
-      data_rows2 > (M2 + 63) / 64)
-    return (int)hipErrorInvalidValue;
-  const int rows = data_rows > data_rows2 ? data_rows : data_rows2;
-  if (rows > BN_WIDE_ROWS) {  // the two-stage folds, one after the other
-    const int rc = mer_bn_finalize_rows(C, M, data_rows, stats, eps, momentum, ms, rmean, rvar, nbt, stream);
-    return rc ? rc : mer_bn_finalize_rows(C2, M2, data_rows2, stats2, eps, momentum, ms2, rmean2, rvar2, nbt2, stream);
-  }
-  BnFinPair t{};
-  t.r[0] = BnFinRec{C, data_rows, M, stats, ms, rmean, rvar, nbt};
-  t.r[1] = BnFinRec{C2, data_rows2, M2, stats2, ms2, rmean2, rvar2, nbt2};
-  const int cmax = C > C2 ? C : C2;
-  const dim3 grid((2 * cmax + 63) / 64, 2);
-  hipStream_t st = (hipStream_t)stream;
-#define MER_BN_FIN2(NB) [&] { hipLaunchKernelGGL(bn_finalize_wide2_kernel<NB>, grid, dim3(1024), 0, st, t, eps, momentum); }
-  wide_pick(rows, MER_BN_FIN2(16), MER_BN_FIN2(32), MER_BN_FIN2(64));
-#undef MER_BN_FIN2
-  MER_LAUNCH_CHECK();
-}
-
-MER_API int mer_bn_finalize_rows(int C, long M, int data_rows, const float* stats, float eps, float momentum, float* ms,
-                                 float* rmean, float* rvar, long long* num_batches_tracked, void* stream) {
-  if (!stats && (!rmean || !rvar)) return (int)hipErrorInvalidValue;
-  const int all_rows = (int)((M + 63) / 64);  // MER_BN_STAT_ROWS(M) - 64: the scratch rows follow them
-  if (data_rows <= 0 || data_rows > all_rows) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = data_rows;
-  const float* src = stats;
-  int rows = tiles;
-  if (stats && tiles > 64 && tiles <= BN_WIDE_ROWS) {
-    const dim3 grid((2 * C + 63) / 64);
-#define MER_BN_FIN_WIDE(NB)                                                                                          \
-  [&] {                                                                                                              \
-    hipLaunchKernelGGL(bn_finalize_wide_kernel<NB>, grid, dim3(1024), 0, st, C, M, tiles, stats, eps, momentum, ms, \
-                       rmean, rvar, num_batches_tracked);                                                            \
-  }
-    wide_pick(tiles, MER_BN_FIN_WIDE(16), MER_BN_FIN_WIDE(32), MER_BN_FIN_WIDE(64));
-#undef MER_BN_FIN_WIDE
-    MER_LAUNCH_CHECK();
-  }
-  if (stats && tiles > 64) {
-    float* scratch = const_cast<float*>(stats) + (long)all_rows * 2 * C;
-    const int per = (tiles + 63) / 64;
-    hipLaunchKernelGGL(bn_stat_rows_fold_kernel, dim3((2 * C + 63) / 64, 64), dim3(256), 0, st, 2 * C, tiles, per,
-                       stats, scratch);
-    src = scratch;
-    rows = 64;
-  }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, st, C, M, rows, src, eps, momentum, ms,
-                     rmean, rvar, num_batches_tracked);
-  MER_LAUNCH_CHECK();
-}
-
-// y = [relu]( bn(x) + (res_bn ? bn2(res) : res) ), 8 channels per thread (C % 8 == 0).
-// ms = (mean, rstd) pairs; eval mode passes (running_mean, 1/sqrt(running_var+eps)) the same way.
-// BN is folded into one (scale, shift) per channel, computed once per block into LDS (C <= 512); a
-// thread always owns the same 8 channels (256 % (C/8) == 0 and the grid stride is a multiple of 256) and
-// streams two 16-byte vectors per iteration so the loads of both are in flight together.
-__global__ __launch_bounds__(256) void bn_apply_kernel(long M, int C, const bf16_t* __restrict__ x,
-                                                       const float* __restrict__ ms, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, const bf16_t* __restrict__ res,
-                                                       const float* __restrict__ ms2, const float* __restrict__ gamma2,
-                                                       const float* __restrict__ beta2, int relu,
-                                                       bf16_t* __restrict__ y) {
-  __shared__ __attribute__((aligned(16))) float coef[4][512];  // scale, shift, scale2, shift2
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float sc = ms[2 * c + 1] * gamma[c];
-    coef[0][c] = sc;
-    coef[1][c] = beta[c] - ms[2 * c] * sc;
-    float sc2 = 1.f, sh2 = 0.f;
-    if (ms2) {
-      sc2 = ms2[2 * c + 1] * gamma2[c];
-      sh2 = beta2[c] - ms2[2 * c] * sc2;
-    }
-    coef[2][c] = sc2;
-    coef[3][c] = sh2;
-  }
-  __syncthreads();
-  const long nvec = M * C / 8;
-  const long stride = (long)gridDim.x * blockDim.x;
-  const long tid0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const int c0 = (int)(tid0 % (C / 8)) * 8;
-  float sc[8], sh[8], sc2[8], sh2[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = coef[0][c0 + i];
-    sh[i] = coef[1][c0 + i];
-    sc2[i] = coef[2][c0 + i];
-    sh2[i] = coef[3][c0 + i];
-  }
-  auto one = [&](const u32x4& xv, const u32x4& rv) -> u32x4 {
-    const bf16_t* xh = reinterpret_cast<const bf16_t*>(&xv);
-    const bf16_t* rh = reinterpret_cast<const bf16_t*>(&rv);
-    u32x4 ov;
-    bf16_t* oh = reinterpret_cast<bf16_t*>(&ov);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float v = bf2f(xh[i]) * sc[i] + sh[i];
-      if (res) v += bf2f(rh[i]) * sc2[i] + sh2[i];
-      if (relu) v = fmaxf(v, 0.f);
-      oh[i] = f2bf(v);
-    }
-    return ov;
-  };
-  const u32x4 z = {0u, 0u, 0u, 0u};
-  long e = tid0;
-  for (; e + stride < nvec; e += 2 * stride) {
-    const u32x4 x0 = *reinterpret_cast<const u32x4*>(x + e * 8);
-    const u32x4 x1 = *reinterpret_cast<const u32x4*>(x + (e + stride) * 8);
-    const u32x4 r0 = res ? *reinterpret_cast<const u32x4*>(res + e * 8) : z;
-    const u32x4 r1 = res ? *reinterpret_cast<const u32x4*>(res + (e + stride) * 8) : z;
-    *reinterpret_cast<u32x4*>(y + e * 8) = one(x0, r0);
-    *reinterpret_cast<u32x4*>(y + (e + stride) * 8) = one(x1, r1);
-  }
-  if (e < nvec) {
-    const u32x4 x0 = *reinterpret_cast<const u32x4*>(x + e * 8);
-    const u32x4 r0 = res ? *reinterpret_cast<const u32x4*>(res + e * 8) : z;
-    *reinterpret_cast<u32x4*>(y + e * 8) = one(x0, r0);
-  }
-}
-static int bn_stream_grid(long nvec) {
-  const long g = (nvec + 1023) / 1024;  // ~4 vectors per thread
-  return (int)(g < 1 ? 1 : g > 2048 ? 2048 : g);
-}
-
-MER_API int mer_bn_apply(long M, int C, const void* x, const float* ms, const float* gamma, const float* beta,
-                         const void* res, const float* ms2, const float* gamma2, const float* beta2, int relu, void* y,
-                         void* stream) {
-  if (C % 8 || C > 512 || 256 % (C / 8)) return (int)hipErrorInvalidValue;
-  const long nvec = M * C / 8;
-  const int grid = bn_stream_grid(nvec);
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, M, C, (const bf16_t*)x, ms,
-                     gamma, beta, (const bf16_t*)res, ms2, gamma2, beta2, relu, (bf16_t*)y);
-  MER_LAUNCH_CHECK();
-}
-
-// BatchNorm folded to (scale, shift) for channel c from ms = (mean, rstd) pairs
-__device__ __forceinline__ void stem_bn_coef(int c, const float* ms, const float* gamma, const float* beta, float& sc,
-                                             float& sh) {
-  sc = ms[2 * c + 1] * gamma[c];
-  sh = beta[c] - ms[2 * c] * sc;
-}
-
-// BN backward reduction: g = dy * (mask > 0) (mask = the ReLU output, or null), xhat from x and ms:
-//   red[c] = (sum g, sum g*xhat), one partial row per block folded in block order.  C <= 512, C % 8 == 0.
-// BNMASK: no mask tensor; the ReLU mask is recomputed as bf16(relu(x*scale + shift)) > 0 from (ms, mgamma,
-// mbeta) -- the fused stem, whose activation is never stored.
-template <bool BNMASK>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long M, int C, const bf16_t* __restrict__ dy,
-                                                            const bf16_t* __restrict__ mask,
-                                                            const bf16_t* __restrict__ x, const float* __restrict__ ms,
-                                                            const float* __restrict__ mgamma,
-                                                            const float* __restrict__ mbeta,
-                                                            float* __restrict__ rows, long rows_per_block) {
-  // per-thread sums over this block's rows, then the rows_per_iter threads of a channel chunk meet in LDS in
-  // thread order and the block STORES its partial row: no atomics, deterministic
-  __shared__ float part[2][2048];  // [s1|s2][tr * C + c], rows_per_iter * C <= 2048
-  const int cpr = C / 8;                     // 16B chunks per row
-  const int rows_per_iter = 256 / cpr > 0 ? 256 / cpr : 1;
-  const int tc = threadIdx.x % cpr, tr = threadIdx.x / cpr;
-  const long r0 = blockIdx.x * rows_per_block, r1 = min(M, r0 + rows_per_block);
-  float s1[8] = {0.f}, s2[8] = {0.f};
-  if (tr < rows_per_iter) {
-    float mean[8], rstd[8], msc[8], msh[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      mean[i] = ms[2 * (tc * 8 + i)];
-      rstd[i] = ms[2 * (tc * 8 + i) + 1];
-      if (BNMASK) stem_bn_coef(tc * 8 + i, ms, mgamma, mbeta, msc[i], msh[i]);
-    }
-    // 4 rows per iteration with every load issued first (unconditional, from clamped rows; a row past r1
-    // contributes exact zeros), so a thread has 8-12 loads in flight instead of one row's 2-3: the same rows
-    // in the same order as a one-row loop, bit-identical sums
-    for (long rb = r0 + tr; rb < r1; rb += 4 * rows_per_iter) {
-      u32x4 gv[4], xv[4], mv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const long r = rb + u * rows_per_iter;
-        const long off = (r < r1 ? r : r1 - 1) * C + tc * 8;
-        gv[u] = *reinterpret_cast<const u32x4*>(dy + off);
-        xv[u] = *reinterpret_cast<const u32x4*>(x + off);
-        mv[u] = u32x4{1u, 1u, 1u, 1u};
-        if (!BNMASK && mask) mv[u] = *reinterpret_cast<const u32x4*>(mask + off);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool rowok = rb + u * rows_per_iter < r1;
-        const bf16_t* gh = reinterpret_cast<const bf16_t*>(&gv[u]);
-        const bf16_t* xh = reinterpret_cast<const bf16_t*>(&xv[u]);
-        const bf16_t* mh = reinterpret_cast<const bf16_t*>(&mv[u]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const bool live = BNMASK ? bf2f(f2bf(fmaxf(bf2f(xh[i]) * msc[i] + msh[i], 0.f))) > 0.f
-                                   : (!mask || bf2f(mh[i]) > 0.f);
-          const float g = (live && rowok) ? bf2f(gh[i]) : 0.f;
-          if (rowok) {  // (a select: the loads above are unconditional)
-            s1[i] += g;
-            s2[i] += g * (bf2f(xh[i]) - mean[i]) * rstd[i];
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      part[0][tr * C + tc * 8 + i] = s1[i];
-      part[1][tr * C + tc * 8 + i] = s2[i];
-    }
-  }
-  __syncthreads();
-  float* out = rows + (long)blockIdx.x * C * 2;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    float a = 0.f, b = 0.f;
-    for (int q = 0; q < rows_per_iter; ++q) {
-      a += part[0][q * C + c];
-      b += part[1][q * C + c];
-    }
-    out[2 * c] = a;
-    out[2 * c + 1] = b;
-  }
-}
-// rows_per_block keeps the block count <= 512 (the workspace holds MER_BN_RED_WS_ROWS = 512 + 64 rows)
-static long bn_bwd_reduce_rpb(long M) { return (M + 511) / 512 > 32 ? (M + 511) / 512 : 32; }
-static int partials_fold(int C, int parts, float* in, float* out, hipStream_t st);
-MER_API int mer_bn_bwd_reduce(long M, int C, const void* dy, const void* mask, const void* x, const float* ms,
-                              float* red, float* workspace, void* stream) {
-  if (C % 8 || C > 512) return (int)hipErrorInvalidValue;
-  const long rpb = bn_bwd_reduce_rpb(M);
-  const int blocks = (int)((M + rpb - 1) / rpb);
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, M, C,
-                     (const bf16_t*)dy, (const bf16_t*)mask, (const bf16_t*)x, ms, (const float*)nullptr,
-                     (const float*)nullptr, workspace, rpb);
-  return partials_fold(C, blocks, workspace, red, (hipStream_t)stream);
-}
-
-// out[c] = sum_p in[p][c] over `parts` partial rows of (a, b) pairs (fused-epilogue reductions), in a fixed
-// order; 64 entries per block, the 4 waves split the rows, then meet in LDS.  More than 64 rows are first
-// folded (bn_stat_rows_fold_kernel) into the 64 scratch rows the caller provides after them.
-__global__ __launch_bounds__(256) void partials_sum_kernel(int C, int parts, const float* __restrict__ in,
-                                                           float* __restrict__ out) {
-  __shared__ float part[4][64];
-  const int el = threadIdx.x & 63, pg = threadIdx.x >> 6;
-  const int e = blockIdx.x * 64 + el;
-  float acc = 0.f;
-  {  // parts <= 64: this wave's <= 16 rows all in flight before the first add (same order)
-    const int ec = e < 2 * C ? e : 2 * C - 1;
-    float x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int p = pg + 4 * i;
-      x[i] = in[(long)(p < parts ? p : parts - 1) * 2 * C + ec];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (pg + 4 * i < parts) acc += x[i];
-  }
-  part[pg][el] = acc;
-  __syncthreads();
-  if (pg == 0 && e < 2 * C) out[e] = part[0][el] + part[1][el] + part[2][el] + part[3][el];
-}
-static int partials_fold(int C, int parts, float* in, float* out, hipStream_t st) {
-  const float* src = in;
-  if (parts > 64 && parts <= BN_WIDE_ROWS) {
-    const dim3 grid((2 * C + 63) / 64);
-#define MER_PSUM_WIDE(NB) \
-  [&] { hipLaunchKernelGGL(partials_sum_wide_kernel<NB>, grid, dim3(1024), 0, st, 2 * C, parts, in, out); }
-    wide_pick(parts, MER_PSUM_WIDE(16), MER_PSUM_WIDE(32), MER_PSUM_WIDE(64));
-#undef MER_PSUM_WIDE
-    MER_LAUNCH_CHECK();
-  }
-  if (parts > 64) {
-    float* scratch = in + (long)parts * 2 * C;
-    const int per = (parts + 63) / 64;
-    hipLaunchKernelGGL(bn_stat_rows_fold_kernel, dim3((2 * C + 63) / 64, 64), dim3(256), 0, st, 2 * C, parts, per, in,
-                       scratch);
-    src = scratch;
-    parts = 64;
-  }
-  hipLaunchKernelGGL(partials_sum_kernel, dim3((2 * C + 63) / 64), dim3(256), 0, st, C, parts, src, out);
-  MER_LAUNCH_CHECK();
-}
-MER_API int mer_partials_sum(int C, int parts, float* in, float* out, void* stream) {
-  if (C <= 0 || parts <= 0) return (int)hipErrorInvalidValue;
-  return partials_fold(C, parts, in, out, (hipStream_t)stream);
-}
-
-MER_API int mer_partials_sum2(int C, int parts, float* in, float* out, float* in2, float* out2, void* stream) {
-  if (C <= 0 || parts <= 0 || !in || !out || !in2 || !out2) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  if (parts > BN_WIDE_ROWS) {  // the two-stage folds, one after the other
-    const int rc = partials_fold(C, parts, in, out, st);
-    return rc ? rc : partials_fold(C, parts, in2, out2, st);
-  }
-  const dim3 grid((2 * C + 63) / 64, 2);
-#define MER_PSUM2(NB) \
-  [&] { hipLaunchKernelGGL(partials_sum_wide2_kernel<NB>, grid, dim3(1024), 0, st, 2 * C, parts, in, out, in2, out2); }
-  wide_pick(parts, MER_PSUM2(16), MER_PSUM2(32), MER_PSUM2(64));
-#undef MER_PSUM2
-  MER_LAUNCH_CHECK();
-}
-
-// dx = gamma*rstd*(g - s1/M - xhat*s2/M) (bf16), and (block 0) dgamma += s2, dbeta += s1.
-// Affine in (g, x) once the sums are known: dx = k1*g + k2*x + k0 per channel, the constants computed once
-// per block into LDS; same thread/channel ownership and 2-vector streaming as bn_apply_kernel.
-// (BNMASK as in bn_bwd_reduce_kernel; dy and dx may alias: every element is read, then written, by one thread)
-template <bool BNMASK>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, const bf16_t* dy,
-                                                           const bf16_t* __restrict__ mask,
-                                                           const bf16_t* __restrict__ x, const float* __restrict__ ms,
-                                                           const float* __restrict__ gamma,
-                                                           const float* __restrict__ mbeta,
-                                                           const float* __restrict__ red, int batch_stats,
-                                                           bf16_t* dx, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta) {
-  __shared__ __attribute__((aligned(16))) float coef[5][512];
-  const float invM = 1.f / (float)M;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    if (blockIdx.x == 0) {
-      if (dgamma) dgamma[c] += red[2 * c + 1];
-      if (dbeta) dbeta[c] += red[2 * c];
-    }
-    const float mu = ms[2 * c], rs = ms[2 * c + 1], gr = gamma[c] * rs;
-    // batch statistics (train): the mean/var terms carry gradient; running stats (eval): they do not
-    const float a = batch_stats ? red[2 * c] * invM : 0.f;
-    const float b = batch_stats ? red[2 * c + 1] * invM : 0.f;
-    const float t = gr * b * rs;  // (explicit rounding steps, shared with bn_bwd_apply2_kernel)
-    coef[0][c] = gr;
-    coef[1][c] = -t;
-    coef[2][c] = fmaf(-gr, a, t * mu);
-    if (BNMASK) stem_bn_coef(c, ms, gamma, mbeta, coef[3][c], coef[4][c]);
-  }
-  __syncthreads();
-  const long nvec = M * C / 8;
-  const long stride = (long)gridDim.x * blockDim.x;
-  const long tid0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const int c0 = (int)(tid0 % (C / 8)) * 8;
-  float k1[8], k2[8], k0[8], msc[8], msh[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    k1[i] = coef[0][c0 + i];
-    k2[i] = coef[1][c0 + i];
-    k0[i] = coef[2][c0 + i];
-    msc[i] = BNMASK ? coef[3][c0 + i] : 0.f;
-    msh[i] = BNMASK ? coef[4][c0 + i] : 0.f;
-  }
-  auto one = [&](const u32x4& gv, const u32x4& xv, const u32x4& mv) -> u32x4 {
-    const bf16_t* gh = reinterpret_cast<const bf16_t*>(&gv);
-    const bf16_t* xh = reinterpret_cast<const bf16_t*>(&xv);
-    const bf16_t* mh = reinterpret_cast<const bf16_t*>(&mv);
-    u32x4 ov;
-    bf16_t* oh = reinterpret_cast<bf16_t*>(&ov);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const bool live = BNMASK ? bf2f(f2bf(fmaxf(bf2f(xh[i]) * msc[i] + msh[i], 0.f))) > 0.f
-                               : (!mask || bf2f(mh[i]) > 0.f);
-      const float g = live ? bf2f(gh[i]) : 0.f;
-      oh[i] = f2bf(fmaf(k1[i], g, fmaf(k2[i], bf2f(xh[i]), k0[i])));  // explicit: apply2 rounds the same
-    }
-    return ov;
-  };
-  const u32x4 one16 = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};  // bf16 1.0 (no mask)
-  long e = tid0;
-  for (; e + stride < nvec; e += 2 * stride) {
-    const long e1 = e + stride;
-    const u32x4 g0 = *reinterpret_cast<const u32x4*>(dy + e * 8);
-    const u32x4 g1 = *reinterpret_cast<const u32x4*>(dy + e1 * 8);
-    const u32x4 x0 = *reinterpret_cast<const u32x4*>(x + e * 8);
-    const u32x4 x1 = *reinterpret_cast<const u32x4*>(x + e1 * 8);
-    const u32x4 m0 = (!BNMASK && mask) ? *reinterpret_cast<const u32x4*>(mask + e * 8) : one16;
-    const u32x4 m1 = (!BNMASK && mask) ? *reinterpret_cast<const u32x4*>(mask + e1 * 8) : one16;
-    *reinterpret_cast<u32x4*>(dx + e * 8) = one(g0, x0, m0);
-    *reinterpret_cast<u32x4*>(dx + e1 * 8) = one(g1, x1, m1);
-  }
-  if (e < nvec) {
-    const u32x4 g0 = *reinterpret_cast<const u32x4*>(dy + e * 8);
-    const u32x4 x0 = *reinterpret_cast<const u32x4*>(x + e * 8);
-    const u32x4 m0 = (!BNMASK && mask) ? *reinterpret_cast<const u32x4*>(mask + e * 8) : one16;
-    *reinterpret_cast<u32x4*>(dx + e * 8) = one(g0, x0, m0);
-  }
-}
-MER_API int mer_bn_bwd_apply(long M, int C, const void* dy, const void* mask, const void* x, const float* ms,
-                             const float* gamma, const float* red, int batch_stats, void* dx, float* dgamma,
-                             float* dbeta, void* stream) {
-  if (C % 8 || C > 512 || 256 % (C / 8)) return (int)hipErrorInvalidValue;
-  const long nvec = M * C / 8;
-  const int grid = bn_stream_grid(nvec);
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, M, C,
-                     (const bf16_t*)dy, (const bf16_t*)mask, (const bf16_t*)x, ms, gamma, (const float*)nullptr, red,
-                     batch_stats, (bf16_t*)dx, dgamma, dbeta);
-  MER_LAUNCH_CHECK();
-}
-
-// Two BatchNorm backward applies that read the same gradient and ReLU mask: a stride-2 BasicBlock's bn2 and its
-// downsample BN (the block output relu(bn2(c2) + bn_d(cd)) fans its gradient out to both).  One pass loads g and the
-// mask once for both outputs -- 12 instead of 16 bytes per element and one launch less -- with each output's
-// per-element arithmetic exactly bn_bwd_apply_kernel<false>'s (bit-identical to two launches).
-__global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(long M, int C, const bf16_t* __restrict__ dy,
-                                                            const bf16_t* __restrict__ mask,
-                                                            const bf16_t* __restrict__ x, const float* __restrict__ ms,
-                                                            const float* __restrict__ gamma,
-                                                            const float* __restrict__ red,
-                                                            const bf16_t* __restrict__ x2,
-                                                            const float* __restrict__ ms2,
-                                                            const float* __restrict__ gamma2,
-                                                            const float* __restrict__ red2, int batch_stats,
-                                                            bf16_t* __restrict__ dx, bf16_t* __restrict__ dx2,
-                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                            float* __restrict__ dgamma2, float* __restrict__ dbeta2) {
-  __shared__ __attribute__((aligned(16))) float coef[6][512];
-  const float invM = 1.f / (float)M;
-  for (int c = threadIdx.x; c < C; c += 256) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float* rd = h ? red2 : red;
-      const float* m = h ? ms2 : ms;
-      if (blockIdx.x == 0) {
-        float* dg = h ? dgamma2 : dgamma;
-        float* db = h ? dbeta2 : dbeta;
-        if (dg) dg[c] += rd[2 * c + 1];
-        if (db) db[c] += rd[2 * c];
-      }
-      const float mu = m[2 * c], rs = m[2 * c + 1], gr = (h ? gamma2 : gamma)[c] * rs;
-      const float a = batch_stats ? rd[2 * c] * invM : 0.f;
-      const float b = batch_stats ? rd[2 * c + 1] * invM : 0.f;
-      const float t = gr * b * rs;
-      coef[3 * h + 0][c] = gr;
-      coef[3 * h + 1][c] = -t;
-      coef[3 * h + 2][c] = fmaf(-gr, a, t * mu);
-    }
-  }
-  __syncthreads();
-  const long nvec = M * C / 8;
-  const long stride = (long)gridDim.x * blockDim.x;
-  const long tid0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const int c0 = (int)(tid0 % (C / 8)) * 8;
-  float k[6][8];
-#pragma unroll
-  for (int j = 0; j < 6; ++j)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[j][i] = coef[j][c0 + i];
-  for (long e = tid0; e < nvec; e += stride) {
-    const u32x4 gv = *reinterpret_cast<const u32x4*>(dy + e * 8);
-    const u32x4 mv = *reinterpret_cast<const u32x4*>(mask + e * 8);
-    const u32x4 xv = *reinterpret_cast<const u32x4*>(x + e * 8);
-    const u32x4 x2v = *reinterpret_cast<const u32x4*>(x2 + e * 8);
-    const bf16_t* gh = reinterpret_cast<const bf16_t*>(&gv);
-    const bf16_t* mh = reinterpret_cast<const bf16_t*>(&mv);
-    const bf16_t* xh = reinterpret_cast<const bf16_t*>(&xv);
-    const bf16_t* x2h = reinterpret_cast<const bf16_t*>(&x2v);
-    u32x4 ov, o2v;
-    bf16_t* oh = reinterpret_cast<bf16_t*>(&ov);
-    bf16_t* o2h = reinterpret_cast<bf16_t*>(&o2v);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float g = bf2f(mh[i]) > 0.f ? bf2f(gh[i]) : 0.f;
-      oh[i] = f2bf(fmaf(k[0][i], g, fmaf(k[1][i], bf2f(xh[i]), k[2][i])));
-      o2h[i] = f2bf(fmaf(k[3][i], g, fmaf(k[4][i], bf2f(x2h[i]), k[5][i])));
-    }
-    *reinterpret_cast<u32x4*>(dx + e * 8) = ov;
-    *reinterpret_cast<u32x4*>(dx2 + e * 8) = o2v;
-  }
-}
-MER_API int mer_bn_bwd_apply2(long M, int C, const void* dy, const void* mask, const void* x, const float* ms,
-                              const float* gamma, const float* red, const void* x2, const float* ms2,
-                              const float* gamma2, const float* red2, int batch_stats, void* dx, void* dx2,
-                              float* dgamma, float* dbeta, float* dgamma2, float* dbeta2, void* stream) {
-  if (C % 8 || C > 512 || 256 % (C / 8) || !mask || !x2 || !dx2 || dx == dy || dx2 == dy)
-    return (int)hipErrorInvalidValue;
-  const long nvec = M * C / 8;
-  const int grid = bn_stream_grid(nvec);
-  hipLaunchKernelGGL(bn_bwd_apply2_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, M, C, (const bf16_t*)dy,
-                     (const bf16_t*)mask, (const bf16_t*)x, ms, gamma, red, (const bf16_t*)x2, ms2, gamma2, red2,
-                     batch_stats, (bf16_t*)dx, (bf16_t*)dx2, dgamma, dbeta, dgamma2, dbeta2);
-  MER_LAUNCH_CHECK();
-}
-
-// ---------------------------------------------------------------------------------------
-// MaxPool2d(3, 2, 1) (resnet stem) channel-last, with the argmax tap (0..8) saved for backward.
-// ---------------------------------------------------------------------------------------
-// 8 channels (16 B) per thread; pixel index decomposed with fdiv (N*Ho*Wo < 2^22)
-__global__ void maxpool_fwd_kernel(int N, int H, int W, int C, int Ho, int Wo, const bf16_t* __restrict__ x,
-                                   bf16_t* __restrict__ y, uint8_t* __restrict__ arg) {
-  const int cpr = C / 8;
-  const int total = N * Ho * Wo * cpr;
-  const float inv_cpr = 1.f / cpr, inv_Wo = 1.f / Wo, inv_Ho = 1.f / Ho;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = fdiv(e, inv_cpr);
-    const int c0 = (e - q * cpr) * 8;
-    const int q2 = fdiv(q, inv_Wo);
-    const int ow = q - q2 * Wo;
-    const int n = fdiv(q2, inv_Ho);
-    const int oh = q2 - n * Ho;
-    float best[8];
-    int bi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { best[i] = -INFINITY; bi[i] = 0; }
-    for (int r = 0; r < 3; ++r)
-      for (int s = 0; s < 3; ++s) {
-        const int ih = oh * 2 - 1 + r, iw = ow * 2 - 1 + s;
-        if (ih < 0 || ih >= H || iw < 0 || iw >= W) continue;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(x + (((long)n * H + ih) * W + iw) * C + c0);
-        const bf16_t* vh = reinterpret_cast<const bf16_t*>(&v);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float f = bf2f(vh[i]);
-          if (f > best[i]) { best[i] = f; bi[i] = r * 3 + s; }  // first max wins, like torch
-        }
-      }
-    u32x4 o;
-    bf16_t* oh8 = reinterpret_cast<bf16_t*>(&o);
-    uint2 a;
-    uint8_t* a8 = reinterpret_cast<uint8_t*>(&a);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { oh8[i] = f2bf(best[i]); a8[i] = (uint8_t)bi[i]; }
-    *reinterpret_cast<u32x4*>(y + (long)q * C + c0) = o;
-    *reinterpret_cast<uint2*>(arg + (long)q * C + c0) = a;
-  }
-}
-MER_API int mer_maxpool_fwd(int N, int H, int W, int C, const void* x, void* y, void* argmax, void* stream) {
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo * C / 8;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, N, H, W, C, Ho, Wo,
-                     (const bf16_t*)x, (bf16_t*)y, (uint8_t*)argmax);
-  MER_LAUNCH_CHECK();
-}
-// gather backward: dx[n,h,w,c] = sum of dy over the (<= 4) windows whose argmax is (h,w)
-__global__ void maxpool_bwd_kernel(int N, int H, int W, int C, int Ho, int Wo, const bf16_t* __restrict__ dy,
-                                   const uint8_t* __restrict__ arg, bf16_t* __restrict__ dx) {
-  const int cpr = C / 8;
-  const int total = N * H * W * cpr;
-  const float inv_cpr = 1.f / cpr, inv_W = 1.f / W, inv_H = 1.f / H;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = fdiv(e, inv_cpr);
-    const int c0 = (e - q * cpr) * 8;
-    const int q2 = fdiv(q, inv_W);
-    const int w = q - q2 * W;
-    const int n = fdiv(q2, inv_H);
-    const int h = q2 - n * H;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // the (<= 4) candidate windows: every load unconditional from a clamped window, invalid ones masked by the
-    // tap test (a load under a per-lane branch waits for itself: 4 dependent round trips per thread)
-    u32x4 gq[2][2];
-    uint2 aq[2][2];
-    int tap[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int oh = (h + 1) / 2 - 1 + a, ow = (w + 1) / 2 - 1 + b;
-        const int r = h - (oh * 2 - 1), s = w - (ow * 2 - 1);
-        const bool ok = oh >= 0 && oh < Ho && ow >= 0 && ow < Wo && r >= 0 && r <= 2 && s >= 0 && s <= 2;
-        const int ohc = oh < 0 ? 0 : (oh >= Ho ? Ho - 1 : oh), owc = ow < 0 ? 0 : (ow >= Wo ? Wo - 1 : ow);
-        const long oi = (((long)n * Ho + ohc) * Wo + owc) * C + c0;
-        gq[a][b] = *reinterpret_cast<const u32x4*>(dy + oi);
-        aq[a][b] = *reinterpret_cast<const uint2*>(arg + oi);
-        tap[a][b] = ok ? r * 3 + s : -1;  // -1 matches no argmax
-      }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const bf16_t* gh = reinterpret_cast<const bf16_t*>(&gq[a][b]);
-        const uint8_t* a8 = reinterpret_cast<const uint8_t*>(&aq[a][b]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if ((int)a8[i] == tap[a][b]) acc[i] += bf2f(gh[i]);
-      }
-    u32x4 o;
-    bf16_t* oh8 = reinterpret_cast<bf16_t*>(&o);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) oh8[i] = f2bf(acc[i]);
-    *reinterpret_cast<u32x4*>(dx + (long)q * C + c0) = o;
-  }
-}
-MER_API int mer_maxpool_bwd(int N, int H, int W, int C, const void* dy, const void* argmax, void* dx, void* stream) {
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
-  const long total = (long)N * H * W * C / 8;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, N, H, W, C, Ho, Wo,
-                     (const bf16_t*)dy, (const uint8_t*)argmax, (bf16_t*)dx);
-  MER_LAUNCH_CHECK();
-}
-
-// ---------------------------------------------------------------------------------------
-// Fused ResNet stem tail (video.py:21-23 -> torchvision conv1/bn1/relu/maxpool), channel-last, C = 64:
-//   forward:  p = maxpool3x3s2p1( a ),  a = bf16(relu(x * scale + shift))  -- a is never stored;
-//   backward: da = maxpool gather of dp (materialised once by maxpool_bwd), g = da * (a > 0) with the ReLU
-//             mask recomputed from (x, BN) in the BatchNorm reduction and apply passes, so a is never stored
-//             (gathering dp inside both passes instead was measured 2x slower: DESIGN.md section 4e).
-// Same roundings, tap order and tie rule as bn_apply -> maxpool_fwd / maxpool_bwd -> bn_bwd_*.
-// ---------------------------------------------------------------------------------------
-
-__global__ void stem_bnrelu_maxpool_kernel(int N, int H, int W, int C, int Ho, int Wo, const bf16_t* __restrict__ x,
-                                           const float* __restrict__ ms, const float* __restrict__ gamma,
-                                           const float* __restrict__ beta, bf16_t* __restrict__ y,
-                                           uint8_t* __restrict__ arg) {
-  const int cpr = C / 8;
-  const int total = N * Ho * Wo * cpr;
-  const float inv_cpr = 1.f / cpr, inv_Wo = 1.f / Wo, inv_Ho = 1.f / Ho;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = fdiv(e, inv_cpr);
-    const int c0 = (e - q * cpr) * 8;
-    const int q2 = fdiv(q, inv_Wo);
-    const int ow = q - q2 * Wo;
-    const int n = fdiv(q2, inv_Ho);
-    const int oh = q2 - n * Ho;
-    float sc[8], sh[8], best[8];
-    int bi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      stem_bn_coef(c0 + i, ms, gamma, beta, sc[i], sh[i]);
-      best[i] = -INFINITY;
-      bi[i] = 0;
-    }
-    // all 9 taps loaded first, unconditionally from clamped pixels (branch-free: the loads are in flight
-    // together), out-of-frame taps masked to -inf so they never win; same tap order and first-max tie rule
-    u32x4 v[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int ih = oh * 2 - 1 + t / 3, iw = ow * 2 - 1 + t % 3;
-      const int ihc = ih < 0 ? 0 : (ih >= H ? H - 1 : ih), iwc = iw < 0 ? 0 : (iw >= W ? W - 1 : iw);
-      v[t] = *reinterpret_cast<const u32x4*>(x + (((long)n * H + ihc) * W + iwc) * C + c0);
-    }
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int ih = oh * 2 - 1 + t / 3, iw = ow * 2 - 1 + t % 3;
-      const bool ok = ih >= 0 && ih < H && iw >= 0 && iw < W;
-      const bf16_t* vh = reinterpret_cast<const bf16_t*>(&v[t]);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float f = ok ? bf2f(f2bf(fmaxf(bf2f(vh[i]) * sc[i] + sh[i], 0.f))) : -INFINITY;
-        if (f > best[i]) { best[i] = f; bi[i] = t; }
-      }
-    }
-    u32x4 o;
-    bf16_t* oh8 = reinterpret_cast<bf16_t*>(&o);
-    uint2 a;
-    uint8_t* a8 = reinterpret_cast<uint8_t*>(&a);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { oh8[i] = f2bf(best[i]); a8[i] = (uint8_t)bi[i]; }
-    *reinterpret_cast<u32x4*>(y + (long)q * C + c0) = o;
-    *reinterpret_cast<uint2*>(arg + (long)q * C + c0) = a;
-  }
-}
-
-MER_API int mer_stem_bnrelu_maxpool_fwd(int N, int H, int W, int C, const void* x, const float* ms, const float* gamma,
-                                        const float* beta, void* y, void* argmax, void* stream) {
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || C > 512 || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo * C / 8;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(stem_bnrelu_maxpool_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, N, H, W, C, Ho, Wo,
-                     (const bf16_t*)x, ms, gamma, beta, (bf16_t*)y, (uint8_t*)argmax);
-  MER_LAUNCH_CHECK();
-}
-
-MER_API int mer_stem_pool_bn_bwd(int N, int H, int W, int C, const void* dy, const void* argmax, const void* x,
-                                 const float* ms, const float* gamma, const float* beta, float* red, int batch_stats,
-                                 void* dx, float* dgamma, float* dbeta, float* workspace, void* stream) {
-  if (C % 8 || C > 512 || 256 % (C / 8) || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
-  const hipStream_t st = (hipStream_t)stream;
-  const long M = (long)N * H * W;
-  // 1) maxpool gather backward into dx (as the pre-BN gradient); 2) BN reduction with the ReLU mask
-  // recomputed from (x, BN); 3) BN apply in place over dx (each element read, then written, by one thread)
-  int rc = mer_maxpool_bwd(N, H, W, C, dy, argmax, dx, stream);
-  if (rc) return rc;
-  const long rpb = bn_bwd_reduce_rpb(M);
-  const int blocks = (int)((M + rpb - 1) / rpb);
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, M, C, (const bf16_t*)dx,
-                     (const bf16_t*)nullptr, (const bf16_t*)x, ms, gamma, beta, workspace, rpb);
-  rc = partials_fold(C, blocks, workspace, red, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<true>), dim3(bn_stream_grid(M * C / 8)), dim3(256), 0, st, M, C,
-                     (const bf16_t*)dx, (const bf16_t*)nullptr, (const bf16_t*)x, ms, gamma, beta, red, batch_stats,
-                     (bf16_t*)dx, dgamma, dbeta);
-  MER_LAUNCH_CHECK();
-}
-
-// global average pool (AdaptiveAvgPool2d(1)): NHWC bf16 -> [N, C] fp32; backward broadcasts dy/HW.
-__global__ void avgpool_fwd_kernel(int N, int HW, int C, const bf16_t* __restrict__ x, float* __restrict__ y) {
-  const int n = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  float s = 0.f;
-  for (int p = 0; p < HW; ++p) s += bf2f(x[((long)n * HW + p) * C + c]);
-  y[(long)n * C + c] = s / HW;
-}
-__global__ void avgpool_bwd_kernel(int N, int HW, int C, const float* __restrict__ dy, bf16_t* __restrict__ dx) {
-  const int n = blockIdx.y;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < HW * C; e += gridDim.x * blockDim.x) {
-    const int c = e % C;
-    dx[(long)n * HW * C + e] = f2bf(dy[(long)n * C + c] / HW);
-  }
-}
-MER_API int mer_avgpool_fwd(int N, int HW, int C, const void* x, float* y, void* stream) {
-  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3((C + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, N, HW, C,
-                     (const bf16_t*)x, y);
-  MER_LAUNCH_CHECK();
-}
-MER_API int mer_avgpool_bwd(int N, int HW, int C, const float* dy, void* dx, void* stream) {
-  dim3 grid((HW * C + 255) / 256, N);
-  hipLaunchKernelGGL(avgpool_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, N, HW, C, dy, (bf16_t*)dx);
-  MER_LAUNCH_CHECK();
+  return launch_conv_plan<true>(g, conv_plan(g, true, variant), (hipStream_t)stream);
 }

@@ -574,7 +574,7 @@ def partials_sum(parts_buf, out, rows=None):
 # 1024 leaves only 4 splits (layer4 3x3: 65 -> 58 us).
 # Target workgroups per wgrad launch: 768 (256 / 384 / 512 lose 3.1 / 1.3 / 0.3 % of the step, 1024 loses 0.4 %).
 _WGRAD_WGS = 768
-# The trunk's default wgrad form for the stride-1 3x3 convs with K > 64 output channels (round 6): conv.hip variant 8,
+# The trunk's default wgrad form for the stride-1 3x3 convs with K > 64 output channels (round 6): conv_wgrad.hip variant 8,
 # two K-groups of 8 waves per workgroup (in-workgroup split-K over the pixels).  A launch of it covers the pixels of two
 # one-group splits: half the splits -- and half the fp32 slabs written and folded (~340 of the ~520 MB per step) -- for
 # the same waves per CU, so it targets _WGRAD_WGS / 2 workgroups.  The others keep the one-group ring (4): the
@@ -582,7 +582,7 @@ _WGRAD_WGS = 768
 # standalone, profiles/r06/bench_wgrad_kg.txt), and the stride-2 / 1x1 wgrads, whose slabs are small and whose kernels
 # ran 2-8 us slower each in the serialized trunk (profiles/r06/trunk_table_serial.txt).
 WGRAD_VARIANT = 8
-# conv.hip's strip kernel (explicit variants 9 / 10 only): all nine taps of a 3x3 / stride-1 / pad-1 conv from one LDS
+# conv_wgrad.hip's strip kernel (explicit variants 9 / 10 only): all nine taps of a 3x3 / stride-1 / pad-1 conv from one LDS
 # strip of X rows.  A tile spans every tap, so a split is (C / 64) * (K / tile) workgroups; it targets one 12-wave
 # workgroup per CU.  The automatic choice does not pick it: it sums in another fp32 order than the rings, and over the
 # benchmark's 60 Adam steps that rounding grows into parameter differences far beyond rounding (an element whose
@@ -592,7 +592,7 @@ _WGRAD_STRIP_WGS = 256
 
 
 def wgrad_strip_split_count(N: int, H: int, splits: int) -> int:
-    """The split count a strip wgrad launch (variants 9, 10) asked for ``splits`` really uses (conv.hip
+    """The split count a strip wgrad launch (variants 9, 10) asked for ``splits`` really uses (conv_wgrad.hip
     launch_wgrad_strip): whole image rows per split, each image's pad row counted, every split non-empty."""
     rows = N * (H + 1)
     per = -(-rows // max(1, int(splits)))
@@ -604,7 +604,7 @@ def _wgrad_min_pix(out_elems, tiles):
 
 
 def wgrad_split_count(P: int, splits: int) -> int:
-    """The split count a wgrad launch asked for ``splits`` over P output pixels really uses (conv.hip
+    """The split count a wgrad launch asked for ``splits`` over P output pixels really uses (conv_wgrad.hip
     conv_wgrad_impl): 64-pixel granules per split, every split non-empty."""
     splits = max(1, int(splits))
     pps = (-(-P // splits) + 63) // 64 * 64

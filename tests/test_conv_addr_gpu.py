@@ -1,8 +1,8 @@
-"""Incremental im2col addressing of the pipelined convolutions (csrc/conv.hip): conv_pipe_kernel's scalar tap walk
-(forward, stride-1 and parity-class input gradients, the fused downsample segment) and wgrad_pipe_kernel's pixel
-walk, at the smallest shapes where a hoisted address can go wrong.  The register-staged kernels (conv variant 0,
-wgrad variant 1) compute every address from scratch and are the bit-exact reference; torch is checked with the
-bars of tests/test_resnet_gpu.py."""
+"""Incremental im2col addressing of the pipelined convolutions: conv_pipe_kernel's scalar tap walk (csrc/conv.hip:
+forward, stride-1 and parity-class input gradients, the fused downsample segment) and wgrad_pipe_kernel's pixel
+walk (csrc/conv_wgrad.hip), at the smallest shapes where a hoisted address can go wrong.  The register-staged kernels
+(conv variant 0, wgrad variant 1) compute every address from scratch and are the bit-exact reference; torch is
+checked with the bars of tests/test_resnet_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -1,4 +1,4 @@
-"""The strip weight gradient of the 3x3 / stride-1 / pad-1 convs (csrc/conv.hip wgrad_strip_kernel, variants 9 and 10):
+"""The strip weight gradient of the 3x3 / stride-1 / pad-1 convs (csrc/conv_wgrad.hip wgrad_strip_kernel, variants 9 and 10):
 the reduction over a padded pixel index, all nine taps served from one LDS strip.  Shapes are the smallest at which
 its index walk can go wrong: a full layer1 map, maps smaller than a 64-slot K-step (several images and pad rows in
 one step), H != W, two channel chunks on both axes, and a 1x1 map where every tap but the centre is padding."""

@@ -1,5 +1,6 @@
-"""Instruction mix of the K loops of the pipelined convolutions (csrc/conv.hip), from the compiler's assembly:
-    hipcc <Makefile FLAGS> -S --cuda-device-only conv.hip -o conv.s
+"""Instruction mix of the K loops of the pipelined convolutions (csrc/conv.hip: conv_pipe_kernel; csrc/conv_wgrad.hip:
+wgrad_pipe_kernel), from the compiler's assembly of the unit that holds the kernel:
+    hipcc <Makefile FLAGS> -S --cuda-device-only conv.hip -o conv.s             (or conv_wgrad.hip -o conv_wgrad.s)
     python tools/loop_mix.py conv.s [kernel substring ...]     (default: conv_pipe_kernel wgrad_pipe_kernel)
 Per kernel, every depth-1 loop that holds an MFMA: static counts per wave and trip of v_mfma*, other v_* (and, of
 those, the 32/64-bit integer multiplies), *load_lds*, ds_read* and *saveexec* lines.  Loop membership is LLVM's own

@@ -98,8 +98,8 @@ def run(variants):
 def run_wgrad(variants, bound=False):
     """wgrad_pipe_kernel and wgrad_strip_kernel (same stamp slots): the 3x3 weight gradients of the B=32 step at the
     step's split counts; K-steps per K-group = the split's 64-pixel steps / groups (strip: 64-slot steps of the padded
-    index).  bound: the K-step time of the real loop beside the two diagnostic forms of the timing build (mer_ct_mode:
-    1 = no LDS-DMA issue after the prologue, 2 = fragment reads of the first K-step only)."""
+    index).  bound: the K-step time of the real loop beside the two diagnostic forms of the timing build (mer_wct_mode:
+    1 = no LDS-DMA issue after the prologue, 2 = fragment reads of the first K-step only).  These kernels are in csrc/conv_wgrad.hip, which has a stamp buffer and a mode word of its own (mer_wct_*)."""
     import numpy as np
     import torch
     sys.path.insert(0, str(ROOT))
@@ -132,15 +132,15 @@ def run_wgrad(variants, bound=False):
             fn = lambda: K.conv_wgrad(x, dy, dw, 3, 3, st, 1, variant=v, splits=splits)  # noqa: E731
             per_step = []
             for mode in ((0, 1, 2) if bound else (0,)):
-                assert dll.mer_ct_mode(mode) == 0
+                assert dll.mer_wct_mode(mode) == 0
                 for _ in range(4):
                     fn()
                 torch.cuda.synchronize()
-                assert dll.mer_ctp_reset() == 0
+                assert dll.mer_wct_reset() == 0
                 fn()
                 torch.cuda.synchronize()
                 t = np.zeros((4096, 8), dtype=np.int64)
-                assert dll.mer_ctp_read(ctypes.c_void_p(t.ctypes.data)) == 0
+                assert dll.mer_wct_read(ctypes.c_void_p(t.ctypes.data)) == 0
                 tt = t[(t[:, 0] != 0) & (t[:, 4] != 0)].astype(np.float64)
                 if not len(tt):
                     print(f"{name:12s} wgrad v{v}: no stamps")
@@ -151,7 +151,7 @@ def run_wgrad(variants, bound=False):
                       f"{(tt[:, 4].max() - tt[:, 0].min()) * tick_us:6.2f} | per WG: pro {ph[0]:5.2f} K {ph[1]:6.2f} "
                       f"xchg {ph[2]:5.2f} store {ph[3]:5.2f} | K-steps {steps:5.1f}: {ph[1] / steps:5.3f} us per step",
                       flush=True)
-            assert dll.mer_ct_mode(0) == 0
+            assert dll.mer_wct_mode(0) == 0
             if bound and len(per_step) == 3:
                 print(f"{name:12s} wgrad v{v} K-step us: real {per_step[0]:5.3f} | no DMA issue {per_step[1]:5.3f} | "
                       f"fragment reads hoisted {per_step[2]:5.3f}", flush=True)
