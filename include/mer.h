@@ -133,6 +133,23 @@ int mer_softmax_dropout_fwd(int B, int H, int h, int Lq, int Lk, const float* S,
 int mer_cross_entropy(int B, int C, const float* logits, const long long* labels, float label_smoothing, int late,
                       float* loss, float* dlogits, long long* preds, void* stream);
 
+/* One batch of the validation loop (train.py:262-301) in one launch, with no host sync: the batch's cls loss
+ * and top-1 computed by the kernel of mer_cross_entropy (same row terms, same row-order sum, / B, fp32; outputs
+ * are logits, or probabilities when late = 1), loss = cls + align_weight * align_loss[0] when align_loss (a
+ * nullable device scalar) is given -- the value mer_add_scaled_scalar gives for those operands -- else loss = cls,
+ * all added into an evaluation state of MER_EVAL_STATE_WORDS(C) eight-byte words in device memory that the
+ * caller zeroes when an evaluation starts:
+ *   int64  conf[C*C]   conf[label * C + pred] += 1 per row
+ *   int64  n           += the rows counted in conf
+ *   int64  invalid     += the rows whose label is outside [0, C): counted nowhere else, they index nothing
+ *   double loss_sum, cls_sum, con_sum   += (double)B * (double)value, the reference's
+ *                      ``total += x.item() * labels.size(0)`` (train.py:287-289); con_sum takes align_loss[0] or 0
+ * The counters use int64 vector atomics; the three sums are updated by one thread, launches in stream order, so
+ * a state is bit-reproducible.  preds (nullable, int64 [B]) receives the top-1.  B >= 1, C >= 1. */
+#define MER_EVAL_STATE_WORDS(C) ((long long)(C) * (long long)(C) + 5)
+int mer_eval_accum(int B, int C, const float* outputs, const long long* labels, float label_smoothing, int late,
+                   const float* align_loss, float align_weight, long long* preds, long long* state, void* stream);
+
 /* state = splitmix64(state + golden): the next step's RNG base, computed on the device (graph-capturable). */
 int mer_rng_advance(unsigned long long* state, void* stream);
 

@@ -17,7 +17,18 @@ def __getattr__(name):
     if name == "WavLMAudioEncoder":
         from .wavlm_audio import WavLMAudioEncoder
         return WavLMAudioEncoder
+    # the validation loop and the per-stage epoch driver (src/train.py:247-301, 736-768, 1066-1150; src/eval.py)
+    if name in {"evaluate", "fit", "cosine_scheduler"}:
+        from . import train
+        return getattr(train, name)
+    if name == "EvalMetrics":
+        from .metrics import EvalMetrics
+        return EvalMetrics
+    if name == "evaluate_checkpoint":
+        from .eval import evaluate_checkpoint
+        return evaluate_checkpoint
     raise AttributeError(name)
 
 
-__all__ = ["LIB", "MerKernelError", "available", "lib_path", "FusionModel", "VideoNet", "WavLMAudioEncoder"]
+__all__ = ["LIB", "MerKernelError", "available", "lib_path", "FusionModel", "VideoNet", "WavLMAudioEncoder",
+           "evaluate", "fit", "cosine_scheduler", "EvalMetrics", "evaluate_checkpoint"]

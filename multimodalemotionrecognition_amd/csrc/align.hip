@@ -154,7 +154,9 @@ MER_API int mer_clip_align_bwd(int B, int D, const float* an, const float* vn, c
 }
 
 // out = x + w * y over device scalars (train.py:225 loss = cls_loss + fusion_align_weight * align_loss)
-__global__ void add_scaled_scalar_kernel(const float* x, const float* y, float w, float* out) { *out = *x + w * *y; }
+__global__ void add_scaled_scalar_kernel(const float* x, const float* y, float w, float* out) {
+  *out = add_scaled_f32(*x, *y, w);
+}
 
 MER_API int mer_add_scaled_scalar(const float* x, const float* y, float w, float* out, void* stream) {
   hipLaunchKernelGGL(add_scaled_scalar_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, x, y, w, out);

@@ -63,6 +63,10 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// x + w * y of train.py:225 (loss = cls_loss + fusion_align_weight * align_loss).  One definition for
+// add_scaled_scalar_kernel and the evaluation accumulator: both round (contract the multiply-add) alike.
+__device__ __forceinline__ float add_scaled_f32(float x, float y, float w) { return x + w * y; }
+
 // Counter-based RNG over (seed, index): the same mask is regenerated in backward from the same (seed, index) --
 // no mask tensor is stored.  32-bit arithmetic only (a 64-bit multiply is four quarter-rate VALU ops on CDNA, and
 // the attention / activation dropouts hash every element): the 64-bit seed and index are folded to 32 bits, and

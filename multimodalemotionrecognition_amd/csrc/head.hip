@@ -465,7 +465,8 @@ template <int G>
 __global__ __launch_bounds__(256) void ce_kernel(int B, int C, const float* __restrict__ logits,
                                                  const long long* __restrict__ labels, float eps_ls, int late,
                                                  float* __restrict__ loss, float* __restrict__ dlogits,
-                                                 long long* __restrict__ preds) {
+                                                 long long* __restrict__ preds, const float* __restrict__ align,
+                                                 float align_w, long long* __restrict__ state) {
   constexpr int RPB = 256 / G;  // rows per pass
   __shared__ float rl[RPB];
   __shared__ float total;
@@ -477,7 +478,7 @@ __global__ __launch_bounds__(256) void ce_kernel(int B, int C, const float* __re
     const float* z = logits + (long)(rv ? b : B - 1) * C;
     const long long y = labels[rv ? b : B - 1];
     float term = 0.f;
-    if (preds) {  // top-1 as torch.argmax: NaN counts as the maximum, the lowest index wins among equals
+    if (preds || state) {  // top-1 as torch.argmax: NaN counts as the maximum, the lowest index wins among equals
       float bv = 0.f;
       int bi = C;  // C = no candidate
       for (int c = g; c < C; c += G)
@@ -488,7 +489,17 @@ __global__ __launch_bounds__(256) void ce_kernel(int B, int C, const float* __re
         const int oi = __shfl_xor(bi, off, G);
         if (argmax_better(ov, oi, bv, bi, C)) { bv = ov; bi = oi; }
       }
-      if (g == 0 && rv) preds[b] = bi < C ? bi : 0;
+      const int top = bi < C ? bi : 0;
+      if (g == 0 && rv && preds) preds[b] = top;
+      if (g == 0 && rv && state) {  // confusion counters (int64 vector atomics); a label outside [0, C) indexes nothing
+        unsigned long long* cnt = reinterpret_cast<unsigned long long*>(state);
+        if (y >= 0 && y < C) {
+          atomicAdd(cnt + y * C + top, 1ull);
+          atomicAdd(cnt + (long)C * C, 1ull);
+        } else {
+          atomicAdd(cnt + (long)C * C + 1, 1ull);
+        }
+      }
     }
     if (late) {
       for (int c = g; c < C; c += G) {
@@ -534,20 +545,45 @@ __global__ __launch_bounds__(256) void ce_kernel(int B, int C, const float* __re
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) *loss = total / B;
+  if (threadIdx.x == 0) {
+    const float cls = total / B;
+    if (loss) *loss = cls;
+    if (state) {  // the three running sums: this one thread, launches in stream order (bit-reproducible)
+      const float con = align ? *align : 0.f;
+      const float tot = align ? add_scaled_f32(cls, con, align_w) : cls;
+      double* sums = reinterpret_cast<double*>(state + (long)C * C + 2);
+      sums[0] += (double)B * (double)tot;
+      sums[1] += (double)B * (double)cls;
+      sums[2] += (double)B * (double)con;
+    }
+  }
 }
-MER_API int mer_cross_entropy(int B, int C, const float* logits, const long long* labels, float label_smoothing,
-                              int late, float* loss, float* dlogits, long long* preds, void* stream) {
-  if (B <= 0 || C <= 0) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
+static int launch_ce(int B, int C, const float* logits, const long long* labels, float label_smoothing, int late,
+                     float* loss, float* dlogits, long long* preds, const float* align, float align_w,
+                     long long* state, hipStream_t st) {
 #define MER_CE(G) hipLaunchKernelGGL(ce_kernel<G>, dim3(1), dim3(256), 0, st, B, C, logits, labels, label_smoothing, \
-                                     late, loss, dlogits, preds)
+                                     late, loss, dlogits, preds, align, align_w, state)
   if (C <= 8) MER_CE(8);
   else if (C <= 16) MER_CE(16);
   else if (C <= 32) MER_CE(32);
   else MER_CE(64);
 #undef MER_CE
   MER_LAUNCH_CHECK();
+}
+MER_API int mer_cross_entropy(int B, int C, const float* logits, const long long* labels, float label_smoothing,
+                              int late, float* loss, float* dlogits, long long* preds, void* stream) {
+  if (B <= 0 || C <= 0) return (int)hipErrorInvalidValue;
+  return launch_ce(B, C, logits, labels, label_smoothing, late, loss, dlogits, preds, nullptr, 0.f, nullptr,
+                   (hipStream_t)stream);
+}
+// The same launch with an evaluation state (mer.h): the batch's cls loss and top-1 exactly as above, then
+// conf / n / invalid and the three fp64 sums are added into ``state``.
+MER_API int mer_eval_accum(int B, int C, const float* outputs, const long long* labels, float label_smoothing,
+                           int late, const float* align_loss, float align_weight, long long* preds, long long* state,
+                           void* stream) {
+  if (B <= 0 || C <= 0 || !state) return (int)hipErrorInvalidValue;
+  return launch_ce(B, C, outputs, labels, label_smoothing, late, nullptr, nullptr, preds, align_loss, align_weight,
+                   state, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -204,15 +204,20 @@ def _collate_meta(metas: List[dict]) -> dict:
     return out
 
 
-def shard_indices(n: int, rank: int, world: int, shuffle: bool, seed: int, epoch: int) -> np.ndarray:
+def shard_indices(n: int, rank: int, world: int, shuffle: bool, seed: int, epoch: int,
+                  pad: bool = True) -> np.ndarray:
     """``torch.utils.data.DistributedSampler`` order (drop_last=False): one permutation of ALL items drawn by
     ``torch.randperm`` from a CPU generator seeded with (seed + epoch) on every rank -- the sampler's own draw, so
     the shuffled order is the reference pipeline's --, padded by wrapping to a multiple of ``world``, then every
-    ``world``-th index from ``rank``: every rank sees the same number of items and, across epochs, different clips."""
+    ``world``-th index from ``rank``: every rank sees the same number of items and, across epochs, different clips.
+    ``pad=False`` (evaluation: no clip counted twice): no wrapping, the ranks' shards partition the items exactly
+    and may differ by one item."""
     if shuffle:
         order = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + int(epoch))).numpy()
     else:
         order = np.arange(n)
+    if not pad:
+        return order[rank:n:world]
     total = -(-n // world) * world if n else 0
     if total > n:
         reps = -(-(total - n) // n)
@@ -228,8 +233,9 @@ class ClipLoader:
     ``items``: ``(frames source, wav path, label[, bbox-or-None[, meta dict]])`` per clip.  Data parallelism:
     rank ``rank`` of ``world`` takes a ``DistributedSampler``-style shard of one global permutation
     (``shard_indices``), so all ranks run the same number of steps (a rank with an extra step would block in the
-    gradient all-reduce).  ``workers`` threads decode ahead (``prefetch`` batches).  ``augment``: the reference's
-    train-split audio augmentation (ravdess.py:519-578, bar noise at a drawn SNR; ``bar_noise`` is the 16 kHz
+    gradient all-reduce); ``pad_shards=False`` (evaluation) takes an exact partition instead, with no clip wrapped
+    round to fill the last shard.  ``workers`` threads decode ahead (``prefetch`` batches).  ``augment``: the
+    reference's train-split audio augmentation (ravdess.py:519-578, bar noise at a drawn SNR; ``bar_noise`` is the 16 kHz
     track, else Gaussian noise), drawn from a generator seeded per (seed, epoch, item) so the draws do not depend
     on thread scheduling.  ``augment`` also applies the reference's train-split video augmentation
     (cv2.GaussianBlur(k, 0) + darken + Gaussian noise on the uint8 frames, ravdess.py:366-384) on the device, one
@@ -239,7 +245,8 @@ class ClipLoader:
     def __init__(self, items: Sequence[Tuple], batch_size: int = 32, num_frames: int = 8, size: int = 112,
                  sample_rate: int = 16000, duration_sec: float = 3.0, rank: int = 0, world: int = 1,
                  workers: int = 8, prefetch: int = 2, device="cuda", shuffle: bool = False, seed: int = 0,
-                 drop_last: bool = True, augment: bool = False, bar_noise: Optional[np.ndarray] = None):
+                 drop_last: bool = True, augment: bool = False, bar_noise: Optional[np.ndarray] = None,
+                 pad_shards: bool = True):
         self.all_items = list(items)
         self.rank, self.world = int(rank), max(1, int(world))
         if not 0 <= self.rank < self.world:
@@ -250,15 +257,20 @@ class ClipLoader:
         self.device = torch.device(device)
         self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
         self.augment, self.bar_noise = bool(augment), bar_noise
+        self.pad_shards = bool(pad_shards)
         self.epoch = 0
 
     @property
     def items(self):
         """This rank's items in epoch-0 order."""
-        return [self.all_items[i] for i in shard_indices(len(self.all_items), self.rank, self.world, False, 0, 0)]
+        return [self.all_items[i] for i in shard_indices(len(self.all_items), self.rank, self.world, False, 0, 0,
+                                                           pad=self.pad_shards)]
 
     def num_samples(self) -> int:
-        return -(-len(self.all_items) // self.world) if self.all_items else 0
+        n = len(self.all_items)
+        if not self.pad_shards:  # this rank's part of an exact partition
+            return len(range(self.rank, n, self.world))
+        return -(-n // self.world) if n else 0
 
     def __len__(self):
         n = self.num_samples()
@@ -280,7 +292,8 @@ class ClipLoader:
         return video, audio, labels, _collate_meta([m for _, _, _, m, _ in decoded])
 
     def __iter__(self):
-        order = shard_indices(len(self.all_items), self.rank, self.world, self.shuffle, self.seed, self.epoch)
+        order = shard_indices(len(self.all_items), self.rank, self.world, self.shuffle, self.seed, self.epoch,
+                              pad=self.pad_shards)
         epoch = self.epoch
         self.epoch += 1
         nb = len(self)

@@ -284,6 +284,32 @@ def cross_entropy(logits, labels, loss, dlogits, label_smoothing=0.0, late=False
         loss.data_ptr(), _ptr(dlogits), _ptr(preds), stream_ptr())
 
 
+def eval_state_words(num_classes: int) -> int:
+    """MER_EVAL_STATE_WORDS(C) of include/mer.h: conf[C*C], n, invalid, then the three fp64 sums."""
+    return int(num_classes) * int(num_classes) + 5
+
+
+def eval_accum(outputs, labels, state, label_smoothing=0.0, late=False, align_loss=None, align_weight=0.0,
+               preds=None):
+    """One ``mer_eval_accum`` launch: adds the batch into ``state`` (int64 [C*C + 5], zeroed by the caller)."""
+    _check_dev(outputs, labels, state, align_loss, preds)
+    if outputs.dim() != 2 or outputs.dtype != torch.float32 or not outputs.is_contiguous():
+        raise ValueError("outputs must be contiguous fp32 [B, C]")
+    B, C = outputs.shape
+    if B < 1 or C < 1:
+        raise ValueError("eval_accum needs B >= 1 and C >= 1")
+    if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
+        raise ValueError("labels must be contiguous int64 [B]")
+    if state.dtype != torch.int64 or state.numel() != eval_state_words(C) or not state.is_contiguous():
+        raise ValueError("state must be contiguous int64 [C*C + 5]")
+    if preds is not None and (preds.dtype != torch.int64 or preds.numel() != B or not preds.is_contiguous()):
+        raise ValueError("preds must be contiguous int64 [B]")
+    if align_loss is not None and (align_loss.dtype != torch.float32 or align_loss.numel() != 1):
+        raise ValueError("align_loss must be one fp32 device scalar")
+    LIB("mer_eval_accum", B, C, outputs.data_ptr(), labels.data_ptr(), float(label_smoothing), int(late),
+        _ptr(align_loss), float(align_weight), _ptr(preds), state.data_ptr(), stream_ptr())
+
+
 def scale_dev(x, s, y):
     LIB("mer_scale_dev", x.numel(), x.data_ptr(), s.data_ptr(), y.data_ptr(), stream_ptr())
 

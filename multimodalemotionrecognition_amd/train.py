@@ -6,18 +6,26 @@
   backward, Adam step), but losses/preds stay on the device (no per-step ``.item()`` host syncs).
 * ``TrainStep`` -- one explicit step (the unit ``bench.py`` times), with the optional RCCL gradient
   all-reduce between backward and the optimizer.
+* ``evaluate`` -- the validation loop of train.py:247-301 with its loss sums and confusion counts accumulated on
+  the device (``metrics.EvalMetrics``), read once per evaluation.
+* ``cosine_scheduler`` / ``fit`` -- train.py:736-768 and the epoch loop of train.py:1071-1150 for one stage
+  (validate, step the schedule, keep the best checkpoint, stop early).
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 from torch import nn
 
 from .dist import GradAllReduce
 from .fusion import FusionModel
 from .losses import CrossEntropyLoss, LateNLLLoss, add_scaled
+from .metrics import (EvalMetrics, confusion_from_preds, macro_f1_from_confusion, merge_states,
+                      metrics_from_state)
 from .optim import FusedAdam
 from .video import VideoNet
 from .wavlm_audio import WavLMAudioEncoder
@@ -280,15 +288,121 @@ def train_one_epoch(model: nn.Module, loader, optimizer: FusedAdam, device: torc
 
 def macro_f1(preds: torch.Tensor, targets: torch.Tensor) -> float:
     """sklearn f1_score(average='macro') over the labels present (utils/metrics.py:13-16)."""
-    labels = torch.unique(torch.cat([preds, targets]))
-    f1s = []
-    for c in labels:
-        tp = ((preds == c) & (targets == c)).sum().item()
-        fp = ((preds == c) & (targets != c)).sum().item()
-        fn = ((preds != c) & (targets == c)).sum().item()
-        denom = 2 * tp + fp + fn
-        f1s.append(0.0 if denom == 0 else 2 * tp / denom)
-    return float(sum(f1s) / len(f1s)) if f1s else 0.0
+    if preds.numel() == 0:
+        return 0.0
+    return macro_f1_from_confusion(confusion_from_preds(preds, targets))
+
+
+def _unpack_batch(batch):
+    if not isinstance(batch, (tuple, list)) or len(batch) not in (3, 4):
+        raise ValueError("loader batches must be (video, audio, labels[, meta])")
+    return batch[0], batch[1], batch[2]
+
+
+def evaluate(model: nn.Module, loader, device: torch.device, loss_fn: nn.Module, fusion_mode: str,
+             fusion_align_weight: float = 0.0, group=None) -> Dict[str, float]:
+    """train.py:247-301: the validation loop, under ``no_grad`` after ``model.eval()`` (the model is left in eval
+    mode, like the reference; ``TrainStep`` switches back).
+
+    Per batch: the forward, then ONE ``mer_eval_accum`` launch that adds the batch's loss terms and its
+    (label, top-1) counts into a device-resident state (``metrics.EvalMetrics``) -- none of the reference's three
+    ``.item()`` syncs per batch (train.py:287-289); the host reads the state once at the end.  ``late`` mode uses
+    ``LateNLLLoss``'s rule, otherwise ``label_smoothing`` is taken from the ``CrossEntropyLoss`` given.  ``group``:
+    sum the raw state over its ranks first (``metrics.merge_states``), so every rank returns the global metrics
+    (use a loader with ``pad_shards=False`` so no clip is counted twice).  Returns ``metrics_from_state``'s dict:
+    the losses are divided by the samples seen (the reference's ``len(loader.dataset)`` for a loader that drops
+    nothing)."""
+    device = torch.device(device)
+    late = fusion_mode == "late"
+    smoothing = 0.0 if late else float(getattr(loss_fn, "label_smoothing", 0.0))
+    weight = float(fusion_align_weight)
+    take_align = (not late) and weight > 0.0 and hasattr(model, "pop_alignment_loss")
+    totals = None
+    with torch.no_grad():
+        model.eval()
+        for batch in loader:
+            video, audio, labels = _unpack_batch(batch)
+            labels = labels.to(device)
+            if fusion_mode in {"audio", "video"}:
+                outputs = model(audio.to(device) if fusion_mode == "audio" else video.to(device))
+            else:
+                outputs = model(video.to(device), audio.to(device))
+            if totals is None:
+                totals = EvalMetrics(outputs.shape[1], device, label_smoothing=smoothing, late=late,
+                                  align_weight=weight)
+            totals.update(outputs, labels, model.pop_alignment_loss() if take_align else None)
+    if totals is None:  # an empty loader (an empty shard of a distributed evaluation)
+        c = int(getattr(model, "num_classes", 0))
+        state = (np.zeros((c, c), dtype=np.int64), 0, 0, 0.0, 0.0, 0.0)
+    else:
+        state = totals.state()
+    if group is not None:
+        state = merge_states(state, group)
+    if state[2] > 0:
+        raise ValueError(f"{state[2]} labels outside the model's classes were seen during the evaluation")
+    return metrics_from_state(state)
+
+
+def cosine_scheduler(optimizer, epochs_in_stage: int) -> torch.optim.lr_scheduler.LambdaLR:
+    """train.py:736-768: cosine annealing stepped at each epoch's end, with a group-wise floor
+    ``eta_min = max(1e-8, 0.1 * base_lr)`` (a low-lr backbone group is not raised to a global floor) and
+    ``t = min(epoch + 1, T_max)``, so the first ``.step()`` already decays; a group with ``lr <= 0`` keeps it."""
+    t_max = max(1, int(epochs_in_stage))
+    lambdas = []
+    for group in optimizer.param_groups:
+        base = float(group["lr"])
+        if base <= 0.0:
+            lambdas.append(lambda _epoch: 1.0)
+            continue
+        eta_min = max(1e-8, base * 0.1)
+
+        def lr_lambda(epoch: int, _base=base, _min=eta_min, _tmax=t_max) -> float:
+            t = min(epoch + 1, _tmax)
+            cosine = 0.5 * (1.0 + math.cos(math.pi * t / _tmax))
+            return (_min + (_base - _min) * cosine) / _base
+
+        lambdas.append(lr_lambda)
+    return torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda=lambdas)
+
+
+def fit(model: nn.Module, train_loader, val_loader, optimizer, device, loss_fn: nn.Module, fusion_mode: str,
+        epochs: int, *, fusion_align_weight: float = 0.0, scheduler=None, early_stopping_patience: int = 10,
+        checkpoint_path=None, config: Optional[dict] = None, grad_sync: Optional[GradAllReduce] = None, group=None,
+        best_f1: float = -1.0) -> dict:
+    """The epoch loop of train.py:1071-1150 for ONE stage: per epoch ``train_one_epoch``, ``evaluate``, then
+    ``scheduler.step()``; on a strict improvement of the validation F1 the checkpoint is written (rank 0 only when
+    distributed) and the patience counter reset, otherwise the epoch is counted and the loop stops once
+    ``early_stopping_patience > 0`` epochs went by without one.  The two-stage switch stays with the caller: call
+    ``fit`` once per stage (``apply_two_stage_freeze_policy`` / ``build_fusion_stage_optimizer``), passing the
+    returned ``best_f1`` on.  ``train_one_epoch`` / ``evaluate`` / ``save_checkpoint`` are looked up as module
+    globals at call time."""
+    import torch.distributed as td
+
+    from . import dist as D
+
+    g = globals()
+    best_f1, best_epoch, stale, stopped = float(best_f1), None, 0, False
+    history = []
+    for epoch in range(1, int(epochs) + 1):
+        train_metrics = g["train_one_epoch"](model, train_loader, optimizer, device, loss_fn, fusion_mode,
+                                             fusion_align_weight=fusion_align_weight, grad_sync=grad_sync)
+        val_metrics = g["evaluate"](model, val_loader, device, loss_fn, fusion_mode,
+                                    fusion_align_weight=fusion_align_weight, group=group)
+        if scheduler is not None:
+            scheduler.step()
+        history.append({"train": train_metrics, "val": val_metrics,
+                        "lr": [float(pg["lr"]) for pg in optimizer.param_groups]})
+        if val_metrics["f1"] > best_f1:
+            best_f1, best_epoch, stale = float(val_metrics["f1"]), epoch, 0
+            if checkpoint_path is not None and (not D.is_dist() or td.get_rank() == 0):
+                g["save_checkpoint"](model, checkpoint_path, best_f1, config)
+        else:
+            stale += 1
+            if early_stopping_patience > 0 and stale >= early_stopping_patience:
+                stopped = True
+                break
+    return {"best_f1": best_f1, "best_epoch": best_epoch, "epochs_run": len(history), "stopped_early": stopped,
+            "history": history}
 
 
 def save_checkpoint(model: nn.Module, path, val_f1: float, config: Optional[dict] = None) -> None:
