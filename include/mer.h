@@ -744,6 +744,29 @@ int mer_clip_align_bwd(int B, int D, const float* an, const float* vn, const flo
 /* out[0] = x[0] + w * y[0] (device scalars): train.py:225 loss = cls_loss + fusion_align_weight * align_loss. */
 int mer_add_scaled_scalar(const float* x, const float* y, float w, float* out, void* stream);
 
+/* ============================ mel audio path (fp32) ============================ */
+
+/* Log-mel front end (ravdess.py:478-485: MelSpectrogram(16000, n_fft = win_length = 400, hop 160, n_mels) +
+ * AmplitudeToDB): wav fp32 [B] rows of S samples (row stride wav_stride >= S), S >= 201 (reflect padding of 200).
+ * ctab / stab fp32 [400][208]: hann[n] * cos / sin(2 pi n f / 400), columns >= 201 zero; fb fp32 [208][nmp] with
+ * nmp = n_mels rounded up to 16: the mel filterbank, rows >= 201 and columns >= n_mels zero.  out fp32
+ * [B][n_mels][T], T = 1 + S / 160: the mel power, or with to_db 10 * log10(max(power, 1e-10)).  1 <= n_mels <= 128. */
+int mer_log_mel(int B, int S, int n_mels, const float* wav, long wav_stride, const float* ctab, const float* stab,
+                const float* fb, int to_db, float* out, void* stream);
+
+/* One AudioCNN layer in eval mode (audio.py:128-138): Conv2d(Cin, Cout, 3, padding 1) with bias (may be NULL) +
+ * BatchNorm2d on running statistics + ReLU, then MaxPool2d(2) when pool.  x fp32 [B][Cin][H][W], w [Cout][Cin][3][3],
+ * y fp32 [B][Cout][H][W] or, with pool, [B][Cout][H/2][W/2].  Built for (Cin, Cout, pool) = (1, 16, 1), (16, 32, 1)
+ * and (32, 64, 0); wpack: 9 * Cin * Cout floats of scratch for the two MFMA layers (rewritten by every call). */
+int mer_audiocnn_conv(int B, int H, int W, int Cin, int Cout, int pool, const float* x, const float* w,
+                      const float* bias, const float* gamma, const float* beta, const float* rmean, const float* rvar,
+                      float eps, float* wpack, float* y, void* stream);
+
+/* AdaptiveAvgPool2d((1, bins)) + squeeze(2) + transpose(1, 2): x fp32 [B][C][H][W] -> y fp32 [B][bins][C]. */
+int mer_adaptive_avgpool_seq(int B, int C, int H, int W, int bins, const float* x, float* y, void* stream);
+/* The same from the frame trunk's activation layout: x bf16 NHWC [B][H][W][C] -> y fp32 [B][bins][C]. */
+int mer_adaptive_avgpool_seq_nhwc(int B, int H, int W, int C, int bins, const void* x, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

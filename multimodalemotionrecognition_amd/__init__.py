@@ -7,7 +7,7 @@ from ._lib import LIB, MerKernelError, available, lib_path  # noqa: F401
 
 
 def __getattr__(name):
-    # reference-named model classes, imported lazily (src/models/{fusion,video,wavlm_audio}.py)
+    # reference-named model classes, imported lazily (src/models/{fusion,video,wavlm_audio,audio}.py)
     if name == "FusionModel":
         from .fusion import FusionModel
         return FusionModel
@@ -17,6 +17,9 @@ def __getattr__(name):
     if name == "WavLMAudioEncoder":
         from .wavlm_audio import WavLMAudioEncoder
         return WavLMAudioEncoder
+    if name in {"AudioNet", "AudioCNN", "AudioResNet18", "SpecAugment"}:
+        from . import audio
+        return getattr(audio, name)
     # the validation loop and the per-stage epoch driver (src/train.py:247-301, 736-768, 1066-1150; src/eval.py)
     if name in {"evaluate", "fit", "cosine_scheduler"}:
         from . import train
@@ -31,4 +34,4 @@ def __getattr__(name):
 
 
 __all__ = ["LIB", "MerKernelError", "available", "lib_path", "FusionModel", "VideoNet", "WavLMAudioEncoder",
-           "evaluate", "fit", "cosine_scheduler", "EvalMetrics", "evaluate_checkpoint"]
+           "AudioNet", "AudioCNN", "AudioResNet18", "SpecAugment", "evaluate", "fit", "cosine_scheduler", "EvalMetrics", "evaluate_checkpoint"]

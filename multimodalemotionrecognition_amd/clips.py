@@ -11,11 +11,16 @@ decoded uint8 frames / raw waveforms cross PCIe and the batch is assembled in HB
 * ``pad_crop_waveforms`` -- a ragged list of mono waveforms -> ``[B, 1, sample_rate * duration]``
   (ravdess.py:505-513).
 
+* ``log_mel`` -- a waveform batch -> the log-mel spectrogram ``[B, 1, n_mels, T]`` of ``load_audio_mel``
+  (ravdess.py:478-485: ``MelSpectrogram(16000, n_mels=64, win_length=400, hop_length=160)`` + ``AmplitudeToDB()``).
+
 Decoding (cv2.VideoCapture / librosa), face detection / crop and the audio augmentation stay on the host
-(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``; CPU restatement: ``oracle/clips_ref.py``.
+(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``; CPU restatements: ``oracle/clips_ref.py``,
+``tests/mel_ref.py``.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Sequence
 
 import torch
@@ -145,4 +150,72 @@ def pad_crop_waveforms(wavs: Sequence[torch.Tensor], sample_rate: int = 16000, d
     out = torch.empty(len(flat), 1, target, device=dev, dtype=torch.float32)
     K.LIB("mer_wav_pad_crop", len(flat), target, packed.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(),
           out.data_ptr(), K.stream_ptr())
+    return out
+
+
+MEL_N_FFT, MEL_HOP, MEL_BINS, MEL_BINS_PAD = 400, 160, 201, 208
+
+
+def mel_tables(n_mels: int = 64, sample_rate: int = 16000):
+    """Host tables of ``log_mel`` (fp64, rounded to fp32 once): ``(ctab, stab, fb)``.
+
+    ``ctab`` / ``stab`` ``[400][208]``: the periodic Hann window times cos / sin(2 pi n f / 400), so the windowed DFT
+    is one matrix product on the raw frame; ``fb`` ``[208][n_mels rounded up to 16]``: the HTK mel filterbank of
+    ``torchaudio.functional.melscale_fbanks(201, 0, sr / 2, n_mels, sr, norm=None)``.  Padding columns / rows are 0."""
+    n = torch.arange(MEL_N_FFT, dtype=torch.float64)
+    win = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n / MEL_N_FFT)  # torch.hann_window(400, periodic=True)
+    # n * f mod 400 keeps the angle in [0, 2 pi): exact integer arithmetic before the one multiplication
+    nf = torch.remainder(n[:, None] * torch.arange(MEL_BINS, dtype=torch.float64)[None, :], MEL_N_FFT)
+    ang = 2.0 * math.pi * nf / MEL_N_FFT
+    ctab = torch.zeros(MEL_N_FFT, MEL_BINS_PAD, dtype=torch.float64)
+    stab = torch.zeros_like(ctab)
+    ctab[:, :MEL_BINS] = win[:, None] * torch.cos(ang)
+    stab[:, :MEL_BINS] = win[:, None] * torch.sin(ang)
+    all_freqs = torch.linspace(0, sample_rate // 2, MEL_BINS, dtype=torch.float64)
+    m_max = 2595.0 * math.log10(1.0 + (sample_rate / 2.0) / 700.0)
+    m_pts = torch.linspace(0.0, m_max, n_mels + 2, dtype=torch.float64)
+    f_pts = 700.0 * (10.0 ** (m_pts / 2595.0) - 1.0)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - all_freqs[:, None]
+    down, up = -slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]
+    fb = torch.zeros(MEL_BINS_PAD, -(-n_mels // 16) * 16, dtype=torch.float64)
+    fb[:MEL_BINS, :n_mels] = torch.clamp(torch.minimum(down, up), min=0.0)
+    return ctab.float().contiguous(), stab.float().contiguous(), fb.float().contiguous()
+
+
+_MEL_TABLES = {}
+
+
+def log_mel(wav: torch.Tensor, n_mels: int = 64, sample_rate: int = 16000, n_fft: int = 400, win_length: int = 400,
+            hop_length: int = 160, to_db: bool = True) -> torch.Tensor:
+    """Waveforms ``[B, 1, S]`` or ``[B, S]`` fp32 on the GPU -> ``[B, 1, n_mels, 1 + S // 160]`` fp32: the mel power
+    spectrogram in dB (``10 log10(max(mel, 1e-10))``), or the power itself with ``to_db=False``.  Periodic Hann
+    window, ``center=True`` with reflect padding, power 2, HTK mel scale from 0 to ``sample_rate / 2``, no
+    normalisation -- the transform of ravdess.py:478-485, whose only free parameter is ``n_mels``."""
+    if win_length != n_fft:
+        raise ValueError(f"log_mel: win_length {win_length} != n_fft {n_fft} is not built (the reference never uses it)")
+    if n_fft != MEL_N_FFT or hop_length != MEL_HOP:
+        raise ValueError("log_mel is built for n_fft = win_length = 400, hop_length = 160 (ravdess.py:478-483)")
+    if not 1 <= int(n_mels) <= 128:
+        raise ValueError(f"log_mel: n_mels {n_mels} outside 1..128")
+    if wav.dim() == 3 and wav.shape[1] == 1:
+        wav = wav[:, 0]
+    if wav.dim() != 2 or wav.dtype != torch.float32:
+        raise ValueError("log_mel takes fp32 waveforms [B, 1, S] or [B, S]")
+    B, S = wav.shape
+    if S <= n_fft // 2:
+        raise ValueError(f"log_mel: reflect padding of {n_fft // 2} samples needs more than {n_fft // 2} samples, got {S}")
+    if not wav.is_cuda:
+        raise RuntimeError("log_mel runs on the MI355X kernels; move the waveforms to the GPU")
+    if wav.stride(1) != 1 or wav.stride(0) < S:
+        wav = wav.contiguous()
+    key = (wav.device, int(n_mels), int(sample_rate))
+    tabs = _MEL_TABLES.get(key)
+    if tabs is None:
+        tabs = _MEL_TABLES[key] = tuple(t.to(wav.device) for t in mel_tables(int(n_mels), int(sample_rate)))
+    T = 1 + S // MEL_HOP
+    out = torch.empty(B, 1, int(n_mels), T, device=wav.device, dtype=torch.float32)
+    if B:
+        K.LIB("mer_log_mel", B, S, int(n_mels), wav.data_ptr(), wav.stride(0), tabs[0].data_ptr(), tabs[1].data_ptr(),
+              tabs[2].data_ptr(), int(bool(to_db)), out.data_ptr(), K.stream_ptr())
     return out

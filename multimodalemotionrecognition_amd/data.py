@@ -240,14 +240,19 @@ class ClipLoader:
     on thread scheduling.  ``augment`` also applies the reference's train-split video augmentation
     (cv2.GaussianBlur(k, 0) + darken + Gaussian noise on the uint8 frames, ravdess.py:366-384) on the device, one
     ``clips.augment_clips`` launch per batch with per-clip draws from the same generator; it is bit-exact against
-    the restatement in ``oracle/clips_ref.py``, and parity against cv2 itself is unpinned (cv2 is absent here)."""
+    the restatement in ``oracle/clips_ref.py``, and parity against cv2 itself is unpinned (cv2 is absent here).
+    ``audio_features="mel"``: ``audio`` is ``clips.log_mel`` of the waveform batch, ``[B, 1, n_mels, 301]`` (what the
+    mel ``AudioNet`` models take); the default ``"wav"`` yields the waveforms."""
 
     def __init__(self, items: Sequence[Tuple], batch_size: int = 32, num_frames: int = 8, size: int = 112,
                  sample_rate: int = 16000, duration_sec: float = 3.0, rank: int = 0, world: int = 1,
                  workers: int = 8, prefetch: int = 2, device="cuda", shuffle: bool = False, seed: int = 0,
                  drop_last: bool = True, augment: bool = False, bar_noise: Optional[np.ndarray] = None,
-                 pad_shards: bool = True):
+                 pad_shards: bool = True, audio_features: str = "wav", n_mels: int = 64):
         self.all_items = list(items)
+        if audio_features not in ("wav", "mel"):
+            raise ValueError(f"audio_features must be 'wav' or 'mel', got {audio_features!r}")
+        self.audio_features, self.n_mels = audio_features, int(n_mels)
         self.rank, self.world = int(rank), max(1, int(world))
         if not 0 <= self.rank < self.world:
             raise ValueError(f"rank {rank} outside world {world}")
@@ -288,6 +293,8 @@ class ClipLoader:
             video = torch.stack(vids).contiguous()
         audio = clips.pad_crop_waveforms([torch.from_numpy(w) for _, w, _, _, _ in decoded], self.sr, self.dur,
                                          device=self.device)
+        if self.audio_features == "mel":  # RavdessAVDataset's audio item (ravdess.py:607): [B, 1, n_mels, T]
+            audio = clips.log_mel(audio, n_mels=self.n_mels, sample_rate=self.sr)
         labels = torch.tensor([lab for _, _, lab, _, _ in decoded], dtype=torch.long).to(self.device)
         return video, audio, labels, _collate_meta([m for _, _, _, m, _ in decoded])
 

@@ -618,13 +618,14 @@ class FusionModel(nn.Module):
             b, t, c, h, w = video.shape
             v_in = video.view(b * t, c, h, w)
             if not hasattr(self.audio_model, "encode_sequence"):
-                raise NotImplementedError("mel AudioNet fallback (fusion.py:379-384) is out of scope: the north-star "
-                                          "path is WavLM encode_sequence")
+                raise NotImplementedError("the audio_time_conv fallback (fusion.py:379-384) for an audio model without "
+                                          "encode_sequence is not built: WavLMAudioEncoder and AudioNet both have it")
             # The two encoders are independent until the xattn block (fusion.py:369-378): the (frozen,
             # forward-only) audio encoder runs on a side HIP stream concurrently with the frame trunk, so
             # its GEMMs fill the CUs the trunk's smaller convs and BatchNorm passes leave idle.  When
             # prefetch_audio() already started it for this very batch (during the previous step's
             # backward), its result is taken over instead.
+            # an audio model without a WavLM encoder (the mel AudioNet) is never prefetched: it takes the inline path
             kind = "seq" if self.audio_encoder_frozen() else "prefix"
             if self._prefetch_matches(audio, kind):
                 got = self._issue_queued(kind, self._take_prefetched(audio, kind))

@@ -846,6 +846,51 @@ def avgpool_bwd(dy, dx):
     LIB("mer_avgpool_bwd", N, H * W, C, dy.data_ptr(), dx.data_ptr(), stream_ptr())
 
 
+def audiocnn_conv(x, conv, bn, pool):
+    """One AudioCNN layer in eval mode: Conv2d(3, padding 1) with bias + BatchNorm2d on its running statistics + ReLU
+    (+ MaxPool2d(2) when ``pool``), fp32 NCHW.  The scale / shift fold and the weight repack run inside the call, from
+    the modules' live tensors."""
+    _check_dev(x, conv.weight, bn.weight, bn.running_mean)
+    B, Cin, H, W = x.shape
+    Cout = conv.weight.shape[0]
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(conv.weight.shape) != (Cout, Cin, 3, 3) \
+            or (Cin, Cout, bool(pool)) not in ((1, 16, True), (16, 32, True), (32, 64, False)):
+        raise ValueError(f"audiocnn_conv: unsupported layer x{tuple(x.shape)} w{tuple(conv.weight.shape)} pool={pool}")
+    if bn.running_mean is None or bn.weight is None:
+        raise ValueError("audiocnn_conv needs an affine BatchNorm2d with running statistics")
+    ps = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([conv.bias] if conv.bias is not None else [])
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in ps):
+        raise ValueError("audiocnn_conv: parameters must be contiguous fp32")
+    y = torch.empty(B, Cout, H // 2 if pool else H, W // 2 if pool else W, device=x.device, dtype=torch.float32)
+    wpack = _workspace(9 * Cin * Cout, x.device) if Cin > 1 else None
+    LIB("mer_audiocnn_conv", B, H, W, Cin, Cout, int(bool(pool)), x.data_ptr(), conv.weight.data_ptr(),
+        _ptr(conv.bias), bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+        bn.running_var.data_ptr(), float(bn.eps), _ptr(wpack), y.data_ptr(), stream_ptr())
+    return y
+
+
+def adaptive_avgpool_seq(x, bins):
+    """AdaptiveAvgPool2d((1, bins)) + squeeze(2) + transpose(1, 2): fp32 [B, C, H, W] -> [B, bins, C]."""
+    _check_dev(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4:
+        raise ValueError("adaptive_avgpool_seq takes contiguous fp32 [B, C, H, W]")
+    B, C, H, W = x.shape
+    y = torch.empty(B, int(bins), C, device=x.device, dtype=torch.float32)
+    LIB("mer_adaptive_avgpool_seq", B, C, H, W, int(bins), x.data_ptr(), y.data_ptr(), stream_ptr())
+    return y
+
+
+def adaptive_avgpool_seq_nhwc(x, bins):
+    """adaptive_avgpool_seq of a trunk activation: bf16 NHWC [B, H, W, C] -> fp32 [B, bins, C]."""
+    _check_dev(x)
+    if x.dtype != torch.bfloat16 or not x.is_contiguous() or x.dim() != 4:
+        raise ValueError("adaptive_avgpool_seq_nhwc takes contiguous bf16 [B, H, W, C]")
+    B, H, W, C = x.shape
+    y = torch.empty(B, int(bins), C, device=x.device, dtype=torch.float32)
+    LIB("mer_adaptive_avgpool_seq_nhwc", B, H, W, C, int(bins), x.data_ptr(), y.data_ptr(), stream_ptr())
+    return y
+
+
 def softmax_avg_fwd(za, zv, out, pa, pv):
     B, C = za.shape
     LIB("mer_softmax_avg_fwd", B, C, za.data_ptr(), zv.data_ptr(), out.data_ptr(), pa.data_ptr(), pv.data_ptr(),

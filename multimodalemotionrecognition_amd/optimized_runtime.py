@@ -59,12 +59,27 @@ def checkpoint_uses_wavlm(state_dict: Dict[str, torch.Tensor]) -> bool:
     return _has_prefix(list(state_dict), "audio_model.wavlm.", "wavlm.")
 
 
+def checkpoint_uses_resnet_audio(state_dict: Dict[str, torch.Tensor]):
+    """Which mel encoder a checkpoint without "config" holds, from its keys: ``encoder.conv1.`` is AudioResNet18,
+    ``encoder.features.`` is AudioCNN (with or without the ``audio_model.`` prefix); None when it holds neither."""
+    keys = list(state_dict)
+    if _has_prefix(keys, "audio_model.encoder.conv1.", "encoder.conv1."):
+        return True
+    if _has_prefix(keys, "audio_model.encoder.features.", "encoder.features."):
+        return False
+    return None
+
+
 class TorchModelRunner:
     """optimized_runtime.py:44-108 on the MI355X kernels.
 
     ``enable_dynamic_quant`` selects the INT8 linear path (per-tensor symmetric int8 weights, dynamic
     per-row int8 activations, int32 MFMA accumulation) that mirrors ``quantize_dynamic({nn.Linear})``;
     in the reference it is CPU-only (optimized_runtime.py:95-96), here it runs on the GPU.
+
+    Mel checkpoints (``AudioNet``, the reference's default audio model): ``predict_probs`` takes
+    the log-mel batch ``[B, 1, n_mels, T]`` or a waveform batch ``[B, 1, S]``, which it passes through
+    ``clips.log_mel`` first, so the same loader batches serve both kinds of checkpoint.
     """
 
     def __init__(self, checkpoint_path: Optional[str] = None, device: str = "cuda", fallback_fusion: str = "xattn",
@@ -87,6 +102,16 @@ class TorchModelRunner:
         self.use_wavlm = bool(self.config.get("use_wavlm", checkpoint_uses_wavlm(state_dict)))
         self.labels = labels_for_num_classes(self.num_classes)
         kw = {k: self.config.get(k, d) for k, d in _CONFIG_DEFAULTS.items()}
+        self.uses_mel = not self.use_wavlm and self.fusion_mode != "video"
+        if self.uses_mel:
+            if "use_resnet_audio" not in self.config:
+                from_keys = checkpoint_uses_resnet_audio(state_dict)
+                if from_keys is not None:
+                    kw["use_resnet_audio"] = from_keys
+            if enable_dynamic_quant:
+                raise NotImplementedError("enable_dynamic_quant with a mel (AudioNet) checkpoint is not built: INT8 "
+                                          "covers the WavLM models")
+        self.n_mels = int(kw["audio_n_mels"])
         model = build_model(num_classes=self.num_classes, fusion=self.fusion_mode, pretrained_video=False,
                             xattn_head=xattn_head, use_wavlm=self.use_wavlm, **kw)
         missing, unexpected = model.load_state_dict(state_dict, strict=False)
@@ -106,6 +131,9 @@ class TorchModelRunner:
         with torch.inference_mode():
             videos = videos.to(self.device, non_blocking=True)
             audios = audios.to(self.device, non_blocking=True)
+            if self.uses_mel and audios.dim() == 3:  # a waveform batch [B, 1, S] for a mel checkpoint
+                from .clips import log_mel
+                audios = log_mel(audios, n_mels=self.n_mels)
             if self.fusion_mode == "audio":
                 outputs = self.model(audios)
             elif self.fusion_mode == "video":

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from .dist import GradAllReduce
+from .audio import AudioNet
 from .fusion import FusionModel
 from .losses import CrossEntropyLoss, LateNLLLoss, add_scaled
 from .metrics import (EvalMetrics, confusion_from_preds, macro_f1_from_confusion, merge_states,
@@ -45,17 +46,23 @@ def build_model(num_classes: int, fusion: str, pretrained_video: bool = True, xa
     Reference quirk kept on purpose: the reference never forwards the ``xattn_use_emotion_prior*``
     flags to ``FusionModel`` (train.py:454-469, eval.py:182-197), so its checkpoints have no prior
     weights; pass ``forward_emotion_prior_flags=True`` to actually enable the prior-bias path.
-    The mel ``AudioNet`` encoder (use_wavlm=False) is outside the north-star path.
+    ``use_wavlm=False`` builds the mel ``AudioNet`` (audio.py), which runs in eval mode only.
     """
-    if not use_wavlm and fusion in {"audio", "late", "concat", "gated", "xattn", "xattn_concat", "xattn_gated"}:
-        raise NotImplementedError("mel AudioNet (use_wavlm=False) is out of scope; the MI355X path is WavLM")
     tp = dict(temporal_pooling=temporal_pooling, temporal_num_heads=temporal_num_heads,
               temporal_num_layers=temporal_num_layers, temporal_dropout=temporal_dropout)
+
+    def audio_model():
+        if use_wavlm:
+            return WavLMAudioEncoder(num_classes=num_classes, **tp)
+        return AudioNet(num_classes=num_classes, use_resnet=use_resnet_audio, spec_augment=True, **tp)
+
     if fusion == "audio":
-        return WavLMAudioEncoder(num_classes=num_classes, **tp)
+        return audio_model()
     if fusion == "video":
         return VideoNet(num_classes=num_classes, pretrained=pretrained_video, **tp)
-    audio = WavLMAudioEncoder(num_classes=num_classes, **tp)
+    if fusion not in {"late", "concat", "gated", "xattn", "xattn_concat", "xattn_gated"}:
+        raise ValueError(f"Unknown fusion mode: {fusion}")
+    audio = audio_model()
     video = VideoNet(num_classes=num_classes, pretrained=pretrained_video, **tp)
     if fusion in {"late", "concat", "gated"}:
         return FusionModel(audio, video, num_classes=num_classes, mode=fusion, fusion_align_mode=fusion_align_mode,
@@ -66,7 +73,8 @@ def build_model(num_classes: int, fusion: str, pretrained_video: bool = True, xa
                      xattn_emotion_prior_hidden_dim=xattn_emotion_prior_hidden_dim,
                      xattn_emotion_prior_dropout=xattn_emotion_prior_dropout) if forward_emotion_prior_flags else {}
         return FusionModel(audio, video, num_classes=num_classes, mode="xattn", xattn_head=head, d_model=xattn_d_model,
-                           num_heads=xattn_heads, audio_n_mels=768, xattn_attn_dropout=xattn_attn_dropout,
+                           num_heads=xattn_heads, audio_n_mels=768 if use_wavlm else audio_n_mels,
+                           xattn_attn_dropout=xattn_attn_dropout,
                            xattn_stochastic_depth=xattn_stochastic_depth, **tp, **prior)
     raise ValueError(f"Unknown fusion mode: {fusion}")
 
