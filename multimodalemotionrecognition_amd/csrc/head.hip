@@ -395,7 +395,13 @@ MER_API int mer_add_ln_bwd(int rows, int d, int rows_per_sample, const float* dy
   // kernel is latency-bound and wants many blocks (64 rows per block made it 31 us at 256 rows AND at 4,768)
   const int rpb = 16;
   const int nb = (rows + rpb - 1) / rpb;
-  hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(nb), dim3(256), 8 * d * sizeof(float), (hipStream_t)stream, rows, d,
+  const size_t lds = (size_t)8 * d * sizeof(float);
+  // past the 64 KB a launch gets by default (d > 2048) the kernel's dynamic-LDS limit has to be raised first
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&add_ln_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return (int)hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, rows, d,
                      rows_per_sample, dy, s, mean, rstd, gamma, dp_p, seed, site, dx, dr, workspace, rpb);
   hipLaunchKernelGGL(rows_sum_add_kernel, dim3((2 * d + 63) / 64), dim3(1024), 0, (hipStream_t)stream, 2 * d, nb,
                      workspace, d, dgamma, dbeta);

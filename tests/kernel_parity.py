@@ -1,0 +1,378 @@
+"""Direct parity of single fp32 kernels against float64 restatements (a plain helper module, not a conftest).
+
+Every restatement below is the operation written in plain torch on the CPU, evaluated in the dtype ``dt`` it is given:
+float64 is the reference, float32 the same text in the kernels' precision.  ``assert_fp64_parity`` bounds a kernel's
+error by 16 x the error of the float32 restatement: the bar is measured against the reference,
+never against the kernel.
+
+Scalars that cross the C ABI as ``float`` (dropout p, LayerNorm eps, the softmax scale, Adam's hyper-parameters) are
+rounded to float32 before either restatement uses them: ``0.999f != 0.999`` is not a kernel error.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from tests.helpers import dropout_keep
+
+EPS32 = float(np.finfo(np.float32).eps)
+ERF_FAST_ABS = 1.5e-7  # csrc/common.h erf_fast: documented absolute error
+F64, F32 = torch.float64, torch.float32
+
+
+def f32(x) -> float:
+    """The value a Python float has after crossing the ABI as a C float."""
+    return float(np.float32(x))
+
+
+def _max_abs(t) -> float:
+    return float(t.abs().max()) if t.numel() else 0.0
+
+
+def assert_fp64_parity(got, ref64, ref32, extra=0.0, what=""):
+    """err = max|got - ref64| <= 16 * max|ref32 - ref64| + eps32 * max|ref64| + extra; returns err / bar."""
+    got = torch.as_tensor(got).detach().cpu()
+    assert ref64.dtype == F64 and ref32.dtype == F32, what
+    assert tuple(got.shape) == tuple(ref64.shape) == tuple(ref32.shape), (what, got.shape, ref64.shape, ref32.shape)
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite kernel output"
+    err = _max_abs(got.to(F64) - ref64)
+    bar = _max_abs(ref32.to(F64) - ref64)
+    ratio = err / bar if bar > 0 else (0.0 if err == 0 else math.inf)
+    print(f"parity {what}: err={err:.3e} bar={bar:.3e} ratio={ratio:.3f}")
+    bound = 16.0 * bar + EPS32 * _max_abs(ref64) + float(extra)
+    assert err <= bound, f"{what}: err {err:.3e} > {bound:.3e} (bar {bar:.3e}, ratio {ratio:.2f})"
+    return ratio
+
+
+def assert_parity_all(got: dict, ref64: dict, ref32: dict, keys, extra=None, what=""):
+    for k in keys:
+        assert_fp64_parity(got[k], ref64[k], ref32[k], extra=(extra or {}).get(k, 0.0), what=f"{what} {k}")
+
+
+# ---- dropout masks restated on the host (tests/helpers.dropout_keep) ----
+def keep_mask(base, site, idx, p) -> torch.Tensor:
+    """Boolean keep mask of the kernels' dropout_scale at element indices ``idx`` (any shape); all kept at p == 0."""
+    idx = np.asarray(idx, dtype=np.uint64)
+    if p <= 0:
+        return torch.ones(idx.shape, dtype=torch.bool)
+    return torch.from_numpy(dropout_keep(int(base), int(site), idx.reshape(-1), f32(p)).reshape(idx.shape))
+
+
+def drop_scale(keep: torch.Tensor, p, dt) -> torch.Tensor:
+    """keep / (1 - p) in dtype dt (the kernels' 1.0f / (1.0f - p))."""
+    if p <= 0:
+        return keep.to(dt)
+    return keep.to(dt) * (torch.ones((), dtype=dt) / (1 - torch.tensor(f32(p), dtype=dt)))
+
+
+def assert_dropout_parity(got, keep, p, ref64, ref32, extra=0.0, what=""):
+    """The kernel's zeros are the mask's, exactly; the kept values meet the parity bar after scaling by 1/(1-p).
+    ``ref64`` / ``ref32`` are the dropped-out results (mask and scale applied).  Every dropped element must be an exact
+    zero; every kept element must be non-zero unless its reference value is itself indistinguishable from zero under
+    the bar's one-ulp floor (gelu(0), gelu(-6) ~ 6e-9), where a zero says nothing about the mask."""
+    got = torch.as_tensor(got).detach().cpu()
+    live = keep & (ref64.abs() > EPS32 * _max_abs(ref64))
+    assert 2 * int(live.sum()) >= int(keep.sum()), f"{what}: too few kept values are non-zero, the mask check is blind"
+    assert bool((got[~keep] == 0).all()) and bool((got[live] != 0).all()), \
+        f"{what}: the kernel's zeros differ from the restated mask"
+    return assert_fp64_parity(got, ref64, ref32, extra=extra, what=what)
+
+
+# ---- sentinels: outputs are views into wider / longer buffers whose every other element must stay untouched ----
+MARKER = -12345.6789
+
+
+class Guarded:
+    """A strided fp32 view (shape, element strides, offset) into a flat buffer pre-filled with MARKER."""
+
+    def __init__(self, shape, strides, device, offset=3, tail=5, init=None):
+        shape, strides = tuple(int(s) for s in shape), tuple(int(s) for s in strides)
+        span = 1 + sum((n - 1) * s for n, s in zip(shape, strides))
+        self.buf = torch.full((offset + span + tail,), MARKER, dtype=F32, device=device)
+        self.view = self.buf.as_strided(shape, strides, offset)
+        idx = torch.zeros(shape, dtype=torch.int64) + offset
+        for d, (n, s) in enumerate(zip(shape, strides)):
+            sh = [1] * len(shape)
+            sh[d] = n
+            idx = idx + (torch.arange(n, dtype=torch.int64) * s).reshape(sh)
+        self.inside = torch.zeros(self.buf.numel(), dtype=torch.bool)
+        self.inside[idx.reshape(-1)] = True
+        assert int(self.inside.sum()) == int(np.prod(shape)), "the view overlaps itself"
+        assert not bool(self.inside.all()), "no sentinel element: the view covers its whole buffer"
+        if init is not None:
+            self.view.copy_(init.to(device))
+
+    def check(self, what=""):
+        """Every element outside the view is bit-unchanged."""
+        bits = self.buf.detach().cpu().view(torch.int32)
+        want = torch.full((1,), MARKER, dtype=F32).view(torch.int32)
+        bad = (bits != want) & ~self.inside
+        assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements outside the output view were overwritten " \
+                                    f"(first at flat index {int(bad.nonzero()[0])})"
+
+
+def guarded_rows(rows, cols, ld, device, init=None, offset=3):
+    """[rows, cols] with row stride ld > cols."""
+    assert ld > cols
+    return Guarded((rows, cols), (ld, 1), device, offset=offset, init=init)
+
+
+def guarded_flat(shape, device, init=None, offset=4):
+    """A contiguous tensor of ``shape`` with sentinel elements in front of and behind it."""
+    strides, s = [], 1
+    for n in reversed(shape):
+        strides.append(s)
+        s *= n
+    return Guarded(shape, tuple(reversed(strides)), device, offset=offset, tail=7, init=init)
+
+
+def padded_input(t, strides, device, offset=0):
+    """``t`` as a strided device view whose gaps hold NaN: a kernel that reads with the wrong stride shows it."""
+    span = 1 + sum((n - 1) * s for n, s in zip(t.shape, strides))
+    buf = torch.full((offset + span + 4,), float("nan"), dtype=F32, device=device)
+    view = buf.as_strided(tuple(t.shape), tuple(int(s) for s in strides), offset)
+    view.copy_(t.to(device))
+    return view
+
+
+def padded_rows(t, pad, device, offset=0):
+    return padded_input(t, (t.shape[1] + pad, 1), device, offset)
+
+
+# ---- seeded CPU inputs ----
+def gen(seed):
+    return torch.Generator().manual_seed(int(seed))
+
+
+def randn(g, *shape):
+    return torch.randn(*shape, generator=g, dtype=F32)
+
+
+# ======================================================================================================
+# Restatements.  Inputs are float32 CPU tensors; each function converts them to ``dt`` and returns a dict.
+# ======================================================================================================
+def ref_add_ln(x, r, gamma, beta, row_scale, dy, eps, dt):
+    """y = LayerNorm(x + s_b r) with its autograd backward.  ``row_scale``: per-row s_b (None with r None)."""
+    x = x.to(dt).requires_grad_(True)
+    gamma, beta = gamma.to(dt).requires_grad_(True), beta.to(dt).requires_grad_(True)
+    if r is not None:
+        r = r.to(dt).requires_grad_(True)
+        s = x + row_scale.to(dt)[:, None] * r
+    else:
+        s = x + 0
+    mean = s.mean(1)
+    var = ((s - mean[:, None]) ** 2).mean(1)
+    rstd = 1 / torch.sqrt(var + torch.tensor(f32(eps), dtype=dt))
+    y = (s - mean[:, None]) * rstd[:, None] * gamma + beta
+    leaves = [x, gamma, beta] + ([r] if r is not None else [])
+    grads = torch.autograd.grad(y, leaves, dy.to(dt))
+    out = {"y": y, "s": s, "mean": mean, "rstd": rstd, "dx": grads[0], "dgamma": grads[1], "dbeta": grads[2]}
+    if r is not None:
+        out["dr"] = grads[3]
+    return {k: v.detach() for k, v in out.items()}
+
+
+def ref_mean_pool(x, dy, dx0, dt):
+    L = x.shape[1]
+    dx = (dy.to(dt) / L)[:, None, :].expand(x.shape)
+    return {"y": x.to(dt).sum(1) / L, "dx": dx + (dx0.to(dt) if dx0 is not None else 0)}
+
+
+def ref_attn_pool(x, scores, dy, dx0, dt):
+    x, dy = x.to(dt), dy.to(dt)
+    attn = torch.softmax(scores.to(dt), -1)
+    y = torch.einsum("bl,bld->bd", attn, x)
+    g = torch.einsum("bd,bld->bl", dy, x)
+    ds = attn * (g - (attn * g).sum(-1, keepdim=True))
+    dx = attn[:, :, None] * dy[:, None, :]
+    return {"attn": attn, "y": y, "dscores": ds, "dx": dx + (dx0.to(dt) if dx0 is not None else 0)}
+
+
+def ref_gelu_dropout(z, dy, keep, p, dt):
+    z, sc = z.to(dt), drop_scale(keep, p, dt)
+    cdf = 0.5 * (1 + torch.erf(z * (0.5 ** 0.5)))
+    pdf = torch.exp(-0.5 * z * z) * (1 / math.sqrt(2 * math.pi))
+    return {"y": z * cdf * sc, "dz": dy.to(dt) * sc * (cdf + z * pdf)}
+
+
+def ref_add_dropout(x, r, r_period, keep, p, dt):
+    rows = x.shape[0]
+    rr = r.to(dt)[torch.arange(rows) % r_period]
+    return {"y": x.to(dt) + rr * drop_scale(keep, p, dt)}
+
+
+def ref_dropout(x, keep, p, dt):
+    return {"y": x.to(dt) * drop_scale(keep, p, dt)}
+
+
+def ref_relu_dropout_bwd(dy, y, keep, p, dt):
+    return {"dz": torch.where(y > 0, dy.to(dt) * drop_scale(keep, p, dt), torch.zeros((), dtype=dt))}
+
+
+def ref_softmax_dropout(S, scale, dPp, keep, p, dt):
+    """P = softmax(scale S); Pd = P m; dS = P (dPp m - sum_j P dPp m) with m the scaled keep mask."""
+    m = drop_scale(keep, p, dt)
+    P = torch.softmax(S.to(dt) * torch.tensor(f32(scale), dtype=dt), -1)
+    t = dPp.to(dt) * m
+    return {"P": P, "Pd": P * m, "dS": P * (t - (P * t).sum(-1, keepdim=True))}
+
+
+def ref_gate_mix(z, v, a, dout, dv0, da0, dt):
+    z, v, a, dout = z.to(dt), v.to(dt), a.to(dt), dout.to(dt)
+    g = torch.sigmoid(z)[:, None]
+    return {"g": g[:, 0], "out": g * v + (1 - g) * a, "dz": ((dout * (v - a)).sum(1, keepdim=True) * g * (1 - g))[:, 0],
+            "dv": dv0.to(dt) + g * dout, "da": da0.to(dt) + (1 - g) * dout}
+
+
+def ref_token_bias(qt, qp, kt, kp, scale, dbias, dt):
+    qt, qp, kt, kp, scale, dbias = (t.to(dt) for t in (qt, qp, kt, kp, scale, dbias))
+    th = torch.tanh(qt[:, :, None] + kt[:, None, :] + (qp + kp)[:, None, None])
+    g = dbias * scale * (1 - th * th)
+    tot = g.sum((1, 2))
+    return {"out": th * scale, "dqt": g.sum(2), "dkt": g.sum(1), "dqp": tot, "dkp": tot,
+            "dscale_part": (dbias * th).sum((1, 2))}
+
+
+def ref_softmax_avg(za, zv, dout, dt):
+    pa, pv, g = torch.softmax(za.to(dt), -1), torch.softmax(zv.to(dt), -1), dout.to(dt)
+    return {"pa": pa, "pv": pv, "out": 0.5 * (pa + pv), "da": 0.5 * pa * (g - (pa * g).sum(-1, keepdim=True)),
+            "dv": 0.5 * pv * (g - (pv * g).sum(-1, keepdim=True))}
+
+
+def ref_vec_sum(x, out0, dt):
+    return {"out": (x.to(dt).sum() + (out0.to(dt) if out0 is not None else 0)).reshape(1)}
+
+
+def ref_scale_dev(x, s, dt):
+    return {"y": x.to(dt) * s.to(dt)}
+
+
+def ref_adam(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale, dt):
+    """One step of the recurrence documented above adam_kernel (csrc/head.hip); hyper-parameters as C floats."""
+    p, g, m, v = (t.to(dt) for t in (p, g, m, v))
+    lr, b1, b2, eps, wd, gs = (torch.tensor(f32(t), dtype=dt) for t in (lr, b1, b2, eps, wd, grad_scale))
+    st = torch.tensor(float(step), dtype=dt)
+    bc1, bc2 = 1 - b1 ** st, 1 - b2 ** st
+    gr = gs * g + wd * p
+    m = b1 * m + (1 - b1) * gr
+    v = b2 * v + (1 - b2) * gr * gr
+    p = p - (lr / bc1) * m / (torch.sqrt(v) / torch.sqrt(bc2) + eps)
+    return {"p": p, "m": m, "v": v}
+
+
+def _gelu(z):
+    return 0.5 * z * (1 + torch.erf(z * (0.5 ** 0.5)))
+
+
+def ref_gemm(a, b, bias, c0, beta, act, dt):
+    """out = act(a @ b + bias + beta c0) over the last two dims (the epilogue order of gemm_f32_kernel);
+    also the pre-activation z."""
+    z = a.to(dt) @ b.to(dt)
+    if bias is not None:
+        z = z + bias.to(dt)
+    if beta:
+        z = z + c0.to(dt)
+    out = torch.relu(z) if act == "relu" else (_gelu(z) if act == "gelu" else z)
+    return {"out": out, "z": z}
+
+
+def ref_clip_align(a, v, log_scale, dloss, dls0, dt):
+    """The formula of the header comment of csrc/align.hip, with autograd."""
+    a, v = a.to(dt).requires_grad_(True), v.to(dt).requires_grad_(True)
+    ls = log_scale.to(dt).reshape(()).requires_grad_(True)
+    B = a.shape[0]
+    na = a.norm(dim=-1).clamp_min(1e-12)
+    nv = v.norm(dim=-1).clamp_min(1e-12)
+    an, vn = a / na[:, None], v / nv[:, None]
+    s = torch.exp(ls).clamp(max=100.0)
+    logits = s * (an @ vn.t())
+    tgt = torch.arange(B)
+    loss = 0.5 * (torch.nn.functional.cross_entropy(logits, tgt) + torch.nn.functional.cross_entropy(logits.t(), tgt))
+    da, dv, dls = torch.autograd.grad(loss, [a, v, ls], dloss.to(dt).reshape(()), allow_unused=True)
+    dls = torch.zeros((), dtype=dt) if dls is None else dls
+    out = {"an": an, "vn": vn, "norms": torch.cat([na, nv]), "logits": logits, "loss": loss.reshape(1), "da": da,
+           "dv": dv, "dlog_scale": (dls0.to(dt).reshape(()) + dls).reshape(1)}
+    return {k: t.detach() for k, t in out.items()}
+
+
+# ======================================================================================================
+# One small seeded instance of every restatement (tests/test_kernel_parity_cpu.py checks that its float32
+# evaluation is a non-degenerate bar).  name -> fn(dt) -> dict of outputs.
+# ======================================================================================================
+BASE, SITE = 0x1234_5678_9ABC, 7
+
+
+def gelu_z(rows, cols, seed):
+    """z over [-6, 6] with 0 and +-1e-6 among its first elements."""
+    z = (torch.rand(rows, cols, generator=gen(seed), dtype=F32) * 12 - 6).reshape(-1)
+    for i, val in enumerate((0.0, 1e-6, -1e-6, 6.0, -6.0)[:z.numel()]):
+        z[i] = val
+    return z.reshape(rows, cols)
+
+
+def adam_inputs(n, seed):
+    """Gradients bounded away from zero: the update lr * g / (|g| + eps) has slope lr / eps at g = 0, where a
+    rounding of g is amplified without bound in any float32 evaluation, the kernel's and the restatement's alike."""
+    g = gen(seed)
+    p, r = randn(g, n), randn(g, n)
+    grad = torch.sign(r) * (0.1 + r.abs())
+    grad[grad == 0] = 0.1
+    return p, grad, torch.zeros(n), torch.zeros(n)
+
+
+def _instances():
+    g = gen(20261020)
+    inst = {}
+    rows, d, rps = 18, 128, 9
+    x, r, dy = randn(g, rows, d) * 3 + 1, randn(g, rows, d) * 3 + 1, randn(g, rows, d)
+    gamma, beta = randn(g, d), randn(g, d)
+    sc = drop_scale(keep_mask(BASE, SITE, np.arange(rows) // rps, 0.5), 0.5, F32)
+    inst["add_ln"] = lambda dt: ref_add_ln(x, r, gamma, beta, sc, dy, 1e-5, dt)
+    inst["add_ln_no_r"] = lambda dt: ref_add_ln(x, None, gamma, beta, None, dy, 1e-5, dt)
+    xm, dym, dx0 = randn(g, 3, 13, 70), randn(g, 3, 70), randn(g, 3, 13, 70)
+    inst["mean_pool"] = lambda dt: ref_mean_pool(xm, dym, dx0, dt)
+    scores = randn(g, 3, 13) * 3 + 50
+    inst["attn_pool"] = lambda dt: ref_attn_pool(xm, scores, dym, dx0, dt)
+    z, dz = gelu_z(7, 130, 1), randn(g, 7, 130)
+    kz = keep_mask(BASE, SITE, np.arange(7 * 130).reshape(7, 130), 0.3)
+    inst["gelu_dropout"] = lambda dt: ref_gelu_dropout(z, dz, kz, 0.3, dt)
+    xa, ra = randn(g, 12, 70), randn(g, 4, 70)
+    ka = keep_mask(BASE, SITE, np.arange(12 * 70).reshape(12, 70), 0.25)
+    inst["add_dropout"] = lambda dt: ref_add_dropout(xa, ra, 4, ka, 0.25, dt)
+    xd, yd = randn(g, 7, 33), torch.relu(randn(g, 7, 33))
+    kd = keep_mask(BASE, SITE, np.arange(7 * 33).reshape(7, 33), 0.3)
+    inst["dropout"] = lambda dt: ref_dropout(xd, kd, 0.3, dt)
+    inst["relu_dropout_bwd"] = lambda dt: ref_relu_dropout_bwd(xd, yd, kd, 0.3, dt)
+    S, dPp = randn(g, 2, 5, 70) * 4, randn(g, 2, 5, 70)
+    ks = keep_mask(BASE, SITE, np.arange(2 * 5 * 70).reshape(2, 5, 70), 0.2)
+    inst["softmax_dropout"] = lambda dt: ref_softmax_dropout(S, 0.25, dPp, ks, 0.2, dt)
+    zg, vg, ag, dg = randn(g, 5), randn(g, 5, 300), randn(g, 5, 300), randn(g, 5, 300)
+    zg[0], zg[1] = 20.0, -20.0
+    inst["gate_mix"] = lambda dt: ref_gate_mix(zg, vg, ag, dg, vg * 0.5, ag * 0.5, dt)
+    qt, qp, kt, kp, db = randn(g, 2, 17), randn(g, 2), randn(g, 2, 241), randn(g, 2), randn(g, 2, 17, 241)
+    tscale = torch.tensor([0.7])
+    inst["token_bias"] = lambda dt: ref_token_bias(qt, qp, kt, kp, tscale, db, dt)
+    za, zv, dso = randn(g, 6, 70) * 3, randn(g, 6, 70) * 3, randn(g, 6, 70)
+    inst["softmax_avg"] = lambda dt: ref_softmax_avg(za, zv, dso, dt)
+    xs = randn(g, 1000)
+    inst["vec_sum"] = lambda dt: ref_vec_sum(xs, torch.tensor(0.3), dt)
+    inst["scale_dev"] = lambda dt: ref_scale_dev(xs, torch.tensor([0.37]), dt)
+    pa_, ga_, ma_, va_ = adam_inputs(1027, 3)
+    inst["adam"] = lambda dt: ref_adam(pa_, ga_, ma_, va_, 1e-3, 0.9, 0.999, 1e-8, 0.01, 1, 0.5, dt)
+    A, Bm, bias, c0 = randn(g, 65, 33), randn(g, 33, 70), randn(g, 70), randn(g, 65, 70)
+    for act in ("none", "relu", "gelu"):
+        inst[f"gemm_{act}"] = lambda dt, act=act: ref_gemm(A, Bm, bias, c0, 1, act, dt)
+    Ab, Bb, cb = randn(g, 3, 17, 37), randn(g, 3, 37, 19), randn(g, 3, 17, 19)
+    inst["gemm_batched"] = lambda dt: ref_gemm(Ab, Bb, None, cb, 1, "none", dt)
+    ca, cv = randn(g, 5, 70), randn(g, 5, 70)
+    ls, dl, dls0 = torch.tensor([math.log(1 / 0.07)]), torch.tensor([0.7]), torch.tensor([0.25])
+    inst["clip_align"] = lambda dt: ref_clip_align(ca, cv, ls, dl, dls0, dt)
+    return inst
+
+
+INSTANCES = _instances()
+# Outputs that are copies of an input in any precision (no arithmetic): their bar is zero by construction and only
+# the one-ulp floor of assert_fp64_parity applies.  Without a residual the saved pre-norm sum is x itself.
+EXACT_OUTPUTS = {"add_ln_no_r": {"s"}}
