@@ -768,6 +768,29 @@ int mer_adaptive_avgpool_seq(int B, int C, int H, int W, int bins, const float* 
 /* The same from the frame trunk's activation layout: x bf16 NHWC [B][H][W][C] -> y fp32 [B][bins][C]. */
 int mer_adaptive_avgpool_seq_nhwc(int B, int H, int W, int C, int bins, const void* x, float* y, void* stream);
 
+/* ============================ timeline over a recording (timeline.py) ============================
+ * Overlapping windows of one long recording whose frames are encoded once.  idx arrays are DEVICE int32; the Python
+ * wrappers validate them on the host, and the kernels clamp every index into [0, n_src) so that no launch reads
+ * outside its source.  The audio windows are mer_wav_pad_crop rows: offsets into the one recording. */
+
+/* mer_frames_resize_normalize reading source frame idx[n] of the decoded recording frames uint8 [n_src][H0][W0][3]
+ * (frame_stride bytes apart) for output n: out fp32 [n_out][3][S][S], bit-identical to gathering the frames first
+ * (the same per-pixel device function).  NULL frames / idx / out are rejected. */
+int mer_frames_gather_resize_normalize(int n_src, int H0, int W0, const void* frames, long frame_stride, int n_out,
+                                       const int* idx, int S, float mean0, float mean1, float mean2, float std0,
+                                       float std1, float std2, float* out, void* stream);
+
+/* out[r][:] = src[idx[r]][:], fp32 rows of width D (contiguous): src [n_src][D], out [n_out][D].  16-byte loads and
+ * stores when D % 4 == 0 and both bases are 16-byte aligned, scalar otherwise.  The [U][512] frame features of a
+ * recording -> the [Nw * T][512] window slots. */
+int mer_rows_gather(int n_src, int n_out, int D, const float* src, const int* idx, float* out, void* stream);
+
+/* Centred moving average over windows: smoothed[w][c] = sum of probs[k][c] for k in [w - radius, w + radius] clipped
+ * to [0, Nw), summed in ascending k, divided by the number of windows summed (radius 0 reproduces probs bit for bit);
+ * top1[w] = argmax_c smoothed[w][c], the lowest index on ties.  probs / smoothed fp32 [Nw][C] (distinct buffers),
+ * top1 int32 [Nw]. */
+int mer_timeline_smooth(int Nw, int C, int radius, const float* probs, float* smoothed, int* top1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

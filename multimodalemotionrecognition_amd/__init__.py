@@ -30,8 +30,16 @@ def __getattr__(name):
     if name == "evaluate_checkpoint":
         from .eval import evaluate_checkpoint
         return evaluate_checkpoint
+    # the emotion timeline over a recording (timeline.py, optimized_runtime.py)
+    if name in {"plan_windows", "WindowPlan"}:
+        from . import timeline
+        return getattr(timeline, name)
+    if name == "process_recording":
+        from .optimized_runtime import process_recording
+        return process_recording
     raise AttributeError(name)
 
 
 __all__ = ["LIB", "MerKernelError", "available", "lib_path", "FusionModel", "VideoNet", "WavLMAudioEncoder",
-           "AudioNet", "AudioCNN", "AudioResNet18", "SpecAugment", "evaluate", "fit", "cosine_scheduler", "EvalMetrics", "evaluate_checkpoint"]
+           "AudioNet", "AudioCNN", "AudioResNet18", "SpecAugment", "evaluate", "fit", "cosine_scheduler", "EvalMetrics", "evaluate_checkpoint",
+           "plan_windows", "WindowPlan", "process_recording"]

@@ -14,9 +14,12 @@ decoded uint8 frames / raw waveforms cross PCIe and the batch is assembled in HB
 * ``log_mel`` -- a waveform batch -> the log-mel spectrogram ``[B, 1, n_mels, T]`` of ``load_audio_mel``
   (ravdess.py:478-485: ``MelSpectrogram(16000, n_mels=64, win_length=400, hop_length=160)`` + ``AmplitudeToDB()``).
 
+* ``gather_preprocess_frames`` / ``waveform_windows`` -- the same two steps for the overlapping windows of one long
+  recording (``timeline.py``): frames picked by index out of the decoded recording, audio windows as offsets into it.
+
 Decoding (cv2.VideoCapture / librosa), face detection / crop and the audio augmentation stay on the host
-(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``; CPU restatements: ``oracle/clips_ref.py``,
-``tests/mel_ref.py``.
+(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``, ``csrc/timeline.hip``; CPU restatements:
+``oracle/clips_ref.py``, ``tests/mel_ref.py``.
 """
 from __future__ import annotations
 
@@ -42,6 +45,26 @@ def preprocess_frames(frames: torch.Tensor, size: int = 112) -> torch.Tensor:
     out = torch.empty(N, 3, size, size, device=frames.device, dtype=torch.float32)
     K.LIB("mer_frames_resize_normalize", N, H, W, frames.data_ptr(), H * W * 3, size, *IMAGENET_MEAN, *IMAGENET_STD,
           out.data_ptr(), K.stream_ptr())
+    return out
+
+
+def gather_preprocess_frames(frames: torch.Tensor, idx, size: int = 112) -> torch.Tensor:
+    """``preprocess_frames(frames.index_select(0, idx), size)``, bit for bit, without the gathered uint8 copy: output
+    ``n`` is made from frame ``idx[n]`` of the decoded recording ``[N, H, W, 3]`` (repeats and any order allowed), one
+    launch for all of them.  ``idx``: a sequence or an int32 / int64 tensor; every value is checked against ``[0, N)``
+    on the host (``ValueError``) before anything is launched."""
+    if not frames.is_cuda:
+        raise RuntimeError("gather_preprocess_frames runs on the MI355X kernels; move the frames to the GPU")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("frames must be uint8 [N, H, W, 3] (RGB)")
+    frames = frames.contiguous()
+    N, H, W, _ = frames.shape
+    dix = K.checked_index(idx, N, frames.device, "frame index")
+    U = dix.numel()
+    out = torch.empty(U, 3, size, size, device=frames.device, dtype=torch.float32)
+    if U:
+        K.LIB("mer_frames_gather_resize_normalize", N, H, W, frames.data_ptr(), H * W * 3, U, dix.data_ptr(), size,
+              *IMAGENET_MEAN, *IMAGENET_STD, out.data_ptr(), K.stream_ptr())
     return out
 
 
@@ -150,6 +173,34 @@ def pad_crop_waveforms(wavs: Sequence[torch.Tensor], sample_rate: int = 16000, d
     out = torch.empty(len(flat), 1, target, device=dev, dtype=torch.float32)
     K.LIB("mer_wav_pad_crop", len(flat), target, packed.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(),
           out.data_ptr(), K.stream_ptr())
+    return out
+
+
+def waveform_windows(wav: torch.Tensor, starts, lengths, target: int, device=None) -> torch.Tensor:
+    """Windows of ONE recording: mono waveform ``wav`` (fp32, host or device) -> ``[Nw, 1, target]`` on the GPU, row
+    ``w`` = ``wav[starts[w] : starts[w] + lengths[w]]`` zero-padded at the end to ``target`` (``lengths[w] <= target``).
+    Windows may overlap: they are offsets into the one buffer, which crosses PCIe once (plus one copy of the
+    offsets / lengths), through the pad / crop kernel of ``pad_crop_waveforms``."""
+    flat = wav.reshape(-1)
+    if flat.dtype != torch.float32:
+        raise ValueError("waveform_windows takes an fp32 waveform")
+    dev = torch.device(device) if device is not None else (flat.device if flat.is_cuda else None)
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("waveform_windows assembles the windows on the MI355X; pass device='cuda'")
+    meta = torch.stack([torch.as_tensor(starts, dtype=torch.int64).reshape(-1).cpu(),
+                        torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).cpu()])
+    target, n, Nw = int(target), int(flat.numel()), int(meta.shape[1])
+    if target <= 0:
+        raise ValueError(f"target must be positive, got {target}")
+    if Nw and (int(meta.min()) < 0 or int(meta[1].max()) > target or int((meta[0] + meta[1]).max()) > n):
+        raise ValueError(f"a window reaches outside the recording of {n} samples or is longer than target {target}")
+    packed = flat.to(dev).contiguous() if flat.is_cuda else _h2d(flat.contiguous(), dev)
+    if not n:
+        packed = torch.zeros(1, device=dev)
+    meta = _h2d(meta, dev)
+    out = torch.empty(Nw, 1, target, device=dev, dtype=torch.float32)
+    K.LIB("mer_wav_pad_crop", Nw, target, packed.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), out.data_ptr(),
+          K.stream_ptr())
     return out
 
 

@@ -612,7 +612,7 @@ class FusionModel(nn.Module):
             a_logits = self.audio_model(audio) if hidden is None else self.audio_model(audio, hidden=hidden,
                                                                                          drop_seed=drop_seed)
             v_logits = self.video_model(video)
-            return EH.late_probs(a_logits, v_logits)
+            return self._late_tail(a_logits, v_logits)
 
         if self.mode in {"xattn", "xattn_concat", "xattn_gated"}:
             b, t, c, h, w = video.shape
@@ -669,8 +669,39 @@ class FusionModel(nn.Module):
             hidden = self._issue_queued("hidden", hidden)
         a_emb = self.audio_model.encode(audio) if hidden is None else self.audio_model.encode(audio, hidden=hidden)
         v_emb = self.video_model.encode(video)
+        return self._embedding_tail(a_emb, v_emb, drops)
+
+    def _embedding_tail(self, a_emb: torch.Tensor, v_emb: torch.Tensor, drops=None) -> torch.Tensor:
+        """concat / gated from the two encoders' embeddings on: the optional alignment, this step's modality-dropout
+        draw (unless ``drops`` was drawn ahead of an early prefetch) and the head."""
         if self.semantic_alignment is not None:  # fusion.py:417-418
             a_emb, v_emb, self.alignment_loss = self.semantic_alignment(a_emb, v_emb)
         if drops is None:
-            drops = self.modality_dropout.draw() if gated else (False, False)
+            drops = self.modality_dropout.draw() if self.mode == "gated" else (False, False)
         return EH.embedding_head(self, a_emb, v_emb, *drops)
+
+    @staticmethod
+    def _late_tail(a_logits: torch.Tensor, v_logits: torch.Tensor) -> torch.Tensor:
+        """late from the two encoders' logits on (fusion.py:358-363)."""
+        return EH.late_probs(a_logits, v_logits)
+
+    def forward_from_frame_features(self, v_feat: torch.Tensor, audio: torch.Tensor) -> torch.Tensor:
+        """``forward`` from the frame trunk's output on: ``v_feat`` ``[B, T, 512]`` fp32 (``video_model.backbone`` per
+        frame), ``audio`` as ``forward`` takes it.  In eval mode the trunk is a per-frame function (BatchNorm on
+        running statistics), so a caller whose clips share frames -- the overlapping windows of a recording,
+        ``TorchModelRunner.predict_timeline`` -- encodes each frame once and gathers the rows.  Eval only; the audio
+        encoder runs inline on the current stream."""
+        if self.training:
+            raise RuntimeError("forward_from_frame_features is an eval-mode entry point (in training mode BatchNorm "
+                               "makes the trunk a function of the whole batch): call .eval()")
+        _require_device(v_feat, audio)
+        if v_feat.dim() != 3:
+            raise ValueError(f"v_feat must be trunk features [B, T, dim], got {tuple(v_feat.shape)}")
+        self.alignment_loss = None
+        if self.mode in {"xattn", "xattn_concat", "xattn_gated"}:
+            return self.xattn_from_features(v_feat, self.audio_model.encode_sequence(audio))
+        if self.mode not in {"late", "concat", "gated"}:
+            raise ValueError(f"Unknown fusion mode: {self.mode}")
+        if self.mode == "late":
+            return self._late_tail(self.audio_model(audio), self.video_model.forward_from_frame_features(v_feat))
+        return self._embedding_tail(self.audio_model.encode(audio), self.video_model.temporal_pool(v_feat))

@@ -1347,3 +1347,61 @@ class WGradTable:
             raise ValueError("wgrad workspace: fp32 device tensor")
         _launch("xh_wgrad", (len(self.rows),), "mer_xh_wgrad", len(self.rows), tab.ctypes.data, ws.data_ptr(),
                 ws.numel(), stream_ptr())
+
+
+# ---- timeline over a recording (csrc/timeline.hip) ----
+def checked_index(idx, n_src: int, device, what: str = "index") -> torch.Tensor:
+    """``idx`` (a sequence, or an integer tensor on the host or the device) as a contiguous int32 tensor on ``device``,
+    after checking every value against ``[0, n_src)`` ON THE HOST -- a bad index raises ``ValueError`` before anything
+    is launched.  A device tensor is read back for the check (one synchronising copy); a host one is staged pinned."""
+    t = torch.as_tensor(idx)
+    if t.numel() == 0 and t.dim() == 1:  # (an empty list has no integer dtype of its own)
+        t = t.to(torch.int64)
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+        raise ValueError(f"{what} must be a 1-D int32 / int64 array, got {t.dtype} {tuple(t.shape)}")
+    host = t.cpu()
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= int(n_src)):
+        raise ValueError(f"{what} outside [0, {int(n_src)}): min {int(host.min())}, max {int(host.max())}")
+    if t.is_cuda:
+        return t.to(device=device, dtype=torch.int32).contiguous()
+    return host.to(torch.int32).contiguous().pin_memory().to(device, non_blocking=True)
+
+
+def rows_gather(src: torch.Tensor, idx, out: torch.Tensor = None) -> torch.Tensor:
+    """``out[r, :] = src[idx[r], :]`` for fp32 rows ``src [N, D]`` on the GPU (bit-exact): mer_rows_gather."""
+    if not src.is_cuda:
+        raise RuntimeError("rows_gather runs on the MI355X kernels; move the rows to the GPU")
+    if src.dtype != torch.float32 or src.dim() != 2:
+        raise ValueError("rows_gather takes fp32 rows [N, D]")
+    src = src.contiguous()
+    N, D = src.shape
+    dix = checked_index(idx, N, src.device, "rows_gather index")
+    R = dix.numel()
+    if out is None:
+        out = torch.empty(R, D, device=src.device, dtype=torch.float32)
+    elif tuple(out.shape) != (R, D) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"rows_gather out must be contiguous fp32 [{R}, {D}] on {src.device}")
+    if R and D:
+        LIB("mer_rows_gather", N, R, D, src.data_ptr(), dix.data_ptr(), out.data_ptr(), stream_ptr())
+    return out
+
+
+def timeline_smooth(probs: torch.Tensor, radius: int):
+    """Per-window probabilities ``[Nw, C]`` fp32 on the GPU -> ``(smoothed [Nw, C] fp32, top1 [Nw] int32)``: the centred
+    moving average over windows ``[w - radius, w + radius]`` clipped to the recording (ascending order, divided by the
+    number of windows averaged; radius 0 returns the input's bits) and the argmax of each smoothed row, lowest index
+    on ties (mer_timeline_smooth)."""
+    if not probs.is_cuda:
+        raise RuntimeError("timeline_smooth runs on the MI355X kernels; move the probabilities to the GPU")
+    if probs.dtype != torch.float32 or probs.dim() != 2 or probs.shape[1] < 1:
+        raise ValueError("timeline_smooth takes fp32 probabilities [Nw, C]")
+    if int(radius) < 0:
+        raise ValueError(f"smoothing radius must be >= 0, got {radius}")
+    probs = probs.contiguous()
+    Nw, C = probs.shape
+    smoothed = torch.empty_like(probs)
+    top1 = torch.empty(Nw, device=probs.device, dtype=torch.int32)
+    if Nw:
+        LIB("mer_timeline_smooth", Nw, C, min(int(radius), Nw), probs.data_ptr(), smoothed.data_ptr(), top1.data_ptr(),
+            stream_ptr())
+    return smoothed, top1

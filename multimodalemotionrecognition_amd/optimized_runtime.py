@@ -16,6 +16,7 @@ from .train import build_model
 FOUR_CLASS_LABELS = ["neutral_calm", "happy", "negative", "surprised"]
 EIGHT_CLASS_LABELS = ["neutral", "calm", "happy", "sad", "angry", "fearful", "disgust", "surprised"]
 FUSION_MODES = {"audio", "video", "late", "concat", "gated", "xattn", "xattn_concat", "xattn_gated"}
+SAMPLE_RATE = 16000  # the reference's audio rate (ravdess.py:505, WavLM and the mel front end alike)
 
 
 def labels_for_num_classes(num_classes: int) -> List[str]:
@@ -143,6 +144,93 @@ class TorchModelRunner:
             probs = outputs if self.fusion_mode == "late" else _softmax(outputs)
         return probs.detach().cpu()
 
+    def predict_timeline(self, frames_u8: Optional[torch.Tensor], waveform: Optional[torch.Tensor], fps, *,
+                         window_sec: float = 3.0, hop_sec: float = 1.0, frames_per_window: int = 8,
+                         frame_grid: str = "window", include_tail: bool = False, smooth_radius: int = 0,
+                         max_windows_per_batch: int = 64) -> Dict[str, Any]:
+        """One prediction per window over a whole decoded recording, every frame encoded once.
+
+        ``frames_u8`` ``[N, H, W, 3]`` uint8 RGB at ``fps`` and the mono 16 kHz ``waveform`` (fp32, any shape), host
+        or device.  ``timeline.plan_windows`` fixes the windows; the recording crosses PCIe once; the frame trunk runs
+        on the plan's UNIQUE frames only (in eval mode it is a per-frame function), their features are gathered to the
+        windows' slots, the audio windows are offsets into the one waveform, and ``forward_from_frame_features`` runs
+        on at most ``max_windows_per_batch`` windows at a time.  With ``frame_grid="window"`` each row is what
+        ``predict_probs`` gives for that window cut out by hand (same network, other batch shapes);
+        ``frame_grid="shared"`` samples one grid for the whole recording so that overlapping windows share frames.
+
+        ``audio`` mode skips the frame work (``frames_u8`` may be None); ``video`` mode uses the video path only (the
+        waveform then only fixes the recording's length in samples, and may be None: ``round(N / fps * 16000)``).
+
+        Returns ``probs`` / ``smoothed`` ``[Nw, C]`` (``smoothed``: the centred moving average over ``2 *
+        smooth_radius + 1`` windows, clipped to the recording), ``top1`` ``[Nw]`` int32 (argmax of ``smoothed``),
+        ``starts_sec``, ``window_seconds``, ``labels``, ``num_windows``, ``num_unique_frames`` and ``num_frame_slots``
+        (``Nw * T``)."""
+        from . import clips
+        from . import kernels as K
+        from .timeline import plan_windows
+
+        if self.device.type != "cuda":
+            raise RuntimeError("predict_timeline runs on the MI355X kernels; build the runner on a GPU device "
+                               "(device='cuda')")
+        chunk_w, radius = int(max_windows_per_batch), int(smooth_radius)
+        if chunk_w < 1:
+            raise ValueError(f"max_windows_per_batch must be at least 1, got {max_windows_per_batch}")
+        if radius < 0:
+            raise ValueError(f"smooth_radius must be >= 0, got {smooth_radius}")
+        use_video, use_audio = self.fusion_mode != "audio", self.fusion_mode != "video"
+        if use_video:
+            if frames_u8 is None or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+                raise ValueError("frames_u8 must be uint8 [N, H, W, 3] (RGB)")
+            n_frames = int(frames_u8.shape[0])
+        else:
+            n_frames = int(frames_u8.shape[0]) if frames_u8 is not None else 1
+        if waveform is None:
+            if use_audio:
+                raise ValueError(f"{self.fusion_mode} mode needs the recording's waveform")
+            if not float(fps) > 0:
+                raise ValueError(f"fps must be positive, got {fps!r}")
+            n_samples = int(round(n_frames / float(fps) * SAMPLE_RATE))
+        else:
+            if waveform.dtype != torch.float32:
+                raise ValueError("waveform must be fp32")
+            n_samples = int(waveform.numel())
+        plan = plan_windows(n_frames, fps, n_samples, SAMPLE_RATE, window_sec, hop_sec,
+                            frames_per_window if use_video else 1, frame_grid, include_tail)
+        Nw, T = plan.num_windows, plan.frames_per_window
+        U = int(plan.unique_idx.numel()) if use_video else 0
+        with torch.inference_mode():
+            v_feat = audio = None
+            if use_video:
+                frames = frames_u8 if frames_u8.is_cuda else clips._h2d(frames_u8.contiguous(), self.device)
+                x = clips.gather_preprocess_frames(frames, plan.unique_idx)
+                vnet = self.model if self.fusion_mode == "video" else self.model.video_model
+                step = chunk_w * T
+                feats = [vnet.backbone(x[i:i + step]).reshape(-1, vnet.embedding_dim) for i in range(0, U, step)]
+                feats = feats[0] if len(feats) == 1 else torch.cat(feats)
+                v_feat = K.rows_gather(feats, plan.inverse.reshape(-1)).view(Nw, T, vnet.embedding_dim)
+            if use_audio:
+                audio = clips.waveform_windows(waveform, plan.starts, plan.lengths, plan.target, device=self.device)
+                if self.uses_mel:
+                    audio = clips.log_mel(audio, n_mels=self.n_mels)
+            rows = []
+            for i in range(0, Nw, chunk_w):
+                if self.fusion_mode == "audio":
+                    out = self.model(audio[i:i + chunk_w])
+                elif self.fusion_mode == "video":
+                    out = self.model.forward_from_frame_features(v_feat[i:i + chunk_w])
+                else:
+                    out = self.model.forward_from_frame_features(v_feat[i:i + chunk_w], audio[i:i + chunk_w])
+                rows.append(out.contiguous().float() if self.fusion_mode == "late" else _softmax(out))
+            probs = rows[0] if len(rows) == 1 else torch.cat(rows)
+            smoothed, top1 = K.timeline_smooth(probs, radius)
+            # one device-to-host copy: the class indices ride along as exactly representable floats
+            host = torch.cat([probs, smoothed, top1.to(torch.float32)[:, None]], dim=1).cpu()
+        C = probs.shape[1]
+        return {"probs": host[:, :C].contiguous(), "smoothed": host[:, C:2 * C].contiguous(),
+                "top1": host[:, 2 * C].to(torch.int32), "starts_sec": list(plan.starts_sec), "labels": self.labels,
+                "num_windows": Nw, "num_unique_frames": U, "num_frame_slots": Nw * T if use_video else 0,
+                "window_seconds": float(window_sec)}
+
 
 def _softmax(x: torch.Tensor) -> torch.Tensor:
     from . import kernels as K
@@ -159,9 +247,28 @@ def process_batch(runner: TorchModelRunner, videos: List[torch.Tensor], audios: 
     v = torch.stack(videos, dim=0)
     a = torch.stack(audios, dim=0)
     probs = runner.predict_probs(v, a)
+    return [_result_row(runner, row) for row in probs]
+
+
+def _result_row(runner: TorchModelRunner, row: torch.Tensor, top: Optional[int] = None) -> Dict[str, Any]:
+    """One clip's result in the worker's format (inference_worker.py:139-147); ``top``: a top-1 already known."""
+    top = int(row.argmax().item()) if top is None else int(top)
+    return {"labels": runner.labels, "probs": [round(float(p), 6) for p in row.tolist()],
+            "top1": {"label": runner.labels[top], "prob": round(float(row[top].item()), 6)}}
+
+
+def process_recording(runner: TorchModelRunner, frames_u8: Optional[torch.Tensor], waveform: Optional[torch.Tensor],
+                      fps, **kw) -> List[Dict[str, Any]]:
+    """``process_batch`` over a whole recording: ``runner.predict_timeline(frames_u8, waveform, fps, **kw)`` as one
+    dict per window in ``process_batch``'s format, plus the window's ``start_sec`` and ``window_seconds`` (the keys
+    of the streaming session's result, streaming.py:103-115).  With ``smooth_radius > 0`` each dict also carries
+    ``smoothed``: the smoothed row in the same format, its top-1 the device's (lowest index on ties)."""
+    res = runner.predict_timeline(frames_u8, waveform, fps, **kw)
     out = []
-    for row in probs:
-        top = int(row.argmax().item())
-        out.append({"labels": runner.labels, "probs": [round(float(p), 6) for p in row.tolist()],
-                    "top1": {"label": runner.labels[top], "prob": round(float(row[top].item()), 6)}})
+    for w, row in enumerate(res["probs"]):
+        d = _result_row(runner, row)
+        d["start_sec"], d["window_seconds"] = res["starts_sec"][w], res["window_seconds"]
+        if int(kw.get("smooth_radius", 0)) > 0:
+            d["smoothed"] = _result_row(runner, res["smoothed"][w], top=int(res["top1"][w]))
+        out.append(d)
     return out

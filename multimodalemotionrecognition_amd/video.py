@@ -776,3 +776,10 @@ class VideoNet(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return hip_linear(self.encode(x), self.classifier)
+
+    def forward_from_frame_features(self, feat: torch.Tensor) -> torch.Tensor:
+        """``forward`` from the trunk's output on: ``feat`` ``[B, T, 512]`` (``backbone`` per frame) -> logits.  For
+        callers whose clips share frames (``TorchModelRunner.predict_timeline``); eval only, as the fusion model's."""
+        if self.training:
+            raise RuntimeError("forward_from_frame_features is an eval-mode entry point: call .eval()")
+        return hip_linear(self.temporal_pool(feat), self.classifier)
