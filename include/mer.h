@@ -791,6 +791,39 @@ int mer_rows_gather(int n_src, int n_out, int D, const float* src, const int* id
  * top1 int32 [Nw]. */
 int mer_timeline_smooth(int Nw, int C, int radius, const float* probs, float* smoothed, int* top1, void* stream);
 
+/* ============================ live streaming sessions (streaming.py) ============================
+ * Per-session device rings written once and read by every window.  Scalar arguments are checked here, device
+ * descriptor arrays by the Python wrappers on the host; the kernels clamp as well. */
+
+/* Stateful rational polyphase resampler, sr_in -> sr_out with up / down = sr_out / sr_in in lowest terms: scipy
+ * resample_poly's filter (host/mer_io.cpp mer_resample): half = 10 * max(up, down), g = firwin(2 * half + 1,
+ * 1 / max(up, down), Kaiser(5)) * up, output o = sum_k g[k] * xu[o * down + half - k] over the upsampled stream xu.
+ * table fp32 [up][kmax], kmax = 2 * half / up + 1: table[p][t] = g[p + t * up] (0 past the filter's end).  Inputs
+ * before the stream start are 0; output o is emitted by the chunk that brings its newest input floor((o * down +
+ * half) / up), so a stream of n inputs has emitted max(0, (n * up - half - 1) / down + 1) outputs (n when up == down
+ * == 1, a plain copy).  Each sum runs over its taps newest input first, one fmaf per tap: chunked and whole streams
+ * are bit-identical.  chunk fp32 [n_chunk]: the inputs n_in .. n_in + n_chunk - 1 (n_in: inputs consumed before);
+ * hist / hist_new fp32 [hist_len], hist_len == kmax (0 for the copy): the last hist_len inputs before / after this
+ * chunk, two DISTINCT buffers the caller alternates (both launches read hist, one writes hist_new); output number q
+ * is written to ring[q % cap] (a chunk that emits more than cap outputs keeps the last cap); counts int64 [2] receives
+ * (inputs consumed, outputs emitted).  n_chunk == 0 returns 0 without a launch.  Calls of one stream must be
+ * ordered (one HIP stream). */
+int mer_resample_stream(int up, int down, int kmax, const float* table, const float* chunk, long n_chunk, long n_in,
+                        const float* hist, float* hist_new, int hist_len, float* ring, long cap, long* counts,
+                        void* stream);
+
+/* out fp32 [B][target]: row b = the last n = min(count[b], cap, target) samples of ring slot[b] of rings fp32
+ * [n_slots][cap] that end just before position end[b] (in [0, cap)), in time order across the wrap, then target - n
+ * zeros (preprocess.py:319-323: crop from the end, pad at the end).  slot / end / count: DEVICE int64 [B].
+ * B <= 65535. */
+int mer_ring_windows(int B, long target, const float* rings, int n_slots, long cap, const long* slot, const long* end,
+                     const long* count, float* out, void* stream);
+
+/* dst[idx[r]][:] = src[r][:], fp32 rows of width D: src [n_rows][D], dst [n_dst][D], idx DEVICE int32 [n_rows] with
+ * UNIQUE values (checked by the caller: two rows to one destination would race).  16-byte accesses when D % 4 == 0
+ * and both bases are 16-byte aligned, scalar otherwise (as mer_rows_gather). */
+int mer_rows_scatter(int n_dst, int n_rows, int D, const float* src, const int* idx, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

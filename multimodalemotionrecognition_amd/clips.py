@@ -17,8 +17,12 @@ decoded uint8 frames / raw waveforms cross PCIe and the batch is assembled in HB
 * ``gather_preprocess_frames`` / ``waveform_windows`` -- the same two steps for the overlapping windows of one long
   recording (``timeline.py``): frames picked by index out of the decoded recording, audio windows as offsets into it.
 
+* ``ResampleStream`` -- a live stream resampled once, chunk by chunk, into a device ring (``streaming.py``; the
+  windows come out of the rings through ``kernels.ring_windows``).
+
 Decoding (cv2.VideoCapture / librosa), face detection / crop and the audio augmentation stay on the host
-(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``, ``csrc/timeline.hip``; CPU restatements:
+(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``, ``csrc/timeline.hip``, ``csrc/stream.hip``;
+CPU restatements:
 ``oracle/clips_ref.py``, ``tests/mel_ref.py``.
 """
 from __future__ import annotations
@@ -34,15 +38,20 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
-def preprocess_frames(frames: torch.Tensor, size: int = 112) -> torch.Tensor:
-    """``[N, H, W, 3]`` uint8 RGB on the GPU -> ``[N, 3, size, size]`` fp32, normalised."""
+def preprocess_frames(frames: torch.Tensor, size: int = 112, out: torch.Tensor = None) -> torch.Tensor:
+    """``[N, H, W, 3]`` uint8 RGB on the GPU -> ``[N, 3, size, size]`` fp32, normalised (into ``out`` when given: the
+    streaming sessions' frame-ring slots)."""
     if not frames.is_cuda:
         raise RuntimeError("preprocess_frames runs on the MI355X kernels; move the frames to the GPU")
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError("frames must be uint8 [N, H, W, 3] (RGB)")
     frames = frames.contiguous()
     N, H, W, _ = frames.shape
-    out = torch.empty(N, 3, size, size, device=frames.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(N, 3, size, size, device=frames.device, dtype=torch.float32)
+    elif tuple(out.shape) != (N, 3, size, size) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != frames.device:
+        raise ValueError(f"preprocess_frames out must be contiguous fp32 [{N}, 3, {size}, {size}] on {frames.device}")
     K.LIB("mer_frames_resize_normalize", N, H, W, frames.data_ptr(), H * W * 3, size, *IMAGENET_MEAN, *IMAGENET_STD,
           out.data_ptr(), K.stream_ptr())
     return out
@@ -202,6 +211,135 @@ def waveform_windows(wav: torch.Tensor, starts, lengths, target: int, device=Non
     K.LIB("mer_wav_pad_crop", Nw, target, packed.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), out.data_ptr(),
           K.stream_ptr())
     return out
+
+
+def resample_ratio(sr_in: int, sr_out: int = 16000):
+    """``(up, down)``: ``sr_out / sr_in`` in lowest terms."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in <= 0 or sr_out <= 0:
+        raise ValueError(f"sample rates must be positive, got {sr_in} -> {sr_out}")
+    g = math.gcd(sr_in, sr_out)
+    return sr_out // g, sr_in // g
+
+
+def resample_emitted(n_in: int, up: int, down: int) -> int:
+    """Outputs a stream of ``n_in`` inputs has emitted (``ResampleStream``): every output whose newest input
+    ``floor((o * down + half) / up)`` has arrived, ``half = 10 * max(up, down)``; equal rates copy."""
+    if up == 1 and down == 1:
+        return int(n_in)
+    a = int(n_in) * up - 10 * max(up, down) - 1
+    return 0 if a < 0 else a // down + 1
+
+
+def polyphase_table(up: int, down: int) -> torch.Tensor:
+    """fp32 ``[up, kmax]``, ``kmax = 2 * half // up + 1``: scipy ``resample_poly``'s filter by phase.  ``g =
+    firwin(2 * half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up`` in fp64 (windowed sinc, normalised to unit
+    sum), rounded to fp32 once; ``table[p, t] = g[p + t * up]``, 0 past the filter's end."""
+    import numpy as np
+
+    up, down = int(up), int(down)
+    max_rate = max(up, down)
+    half = 10 * max_rate
+    n = 2 * half + 1
+    m = np.arange(n, dtype=np.float64) - half
+    cutoff = 1.0 / max_rate
+    h = cutoff * np.sinc(cutoff * m) * np.kaiser(n, 5.0)
+    g = h / h.sum() * up
+    kmax = 2 * half // up + 1
+    tab = np.zeros(up * kmax, dtype=np.float64)
+    k = np.arange(n)
+    tab[(k % up) * kmax + k // up] = g
+    return torch.from_numpy(tab.astype(np.float32)).view(up, kmax)
+
+
+class ResampleCount:
+    """The two counts of a resampled stream on the host: inputs consumed and outputs emitted.  They follow from the
+    chunk lengths alone, so one object serves as the only host mirror of the device counts: a ``ResampleStream``
+    advances it at every push, and the streaming session's control plane reads (or, where no audio is resampled,
+    advances) the same object."""
+
+    def __init__(self, sr_in: int, sr_out: int = 16000):
+        self.up, self.down = resample_ratio(sr_in, sr_out)
+        self.sr_in, self.n_in, self.n_out = int(sr_in), 0, 0
+
+    def advance(self, n: int) -> int:
+        """``n`` more inputs; returns how many outputs they emit."""
+        self.n_in += int(n)
+        emitted = resample_emitted(self.n_in, self.up, self.down) - self.n_out
+        self.n_out += emitted
+        return emitted
+
+
+_POLYPHASE = {}
+RESAMPLE_MAX_SPAN = 12288  # floats of LDS one workgroup of the resampler may stage (csrc/stream.hip)
+
+
+class ResampleStream:
+    """A stream resampled ONCE, chunk by chunk, into a device ring (mer_resample_stream): ``sr_in`` -> ``sr_out``
+    with scipy ``resample_poly``'s filter, bit-identical however the stream is cut into chunks.  Nothing is
+    synthesised at the live edge: an output waits for the chunk that brings its newest input, a latency of
+    ``10 * max(up, down) / up`` input samples.
+
+    Device state: ``hist`` fp32 ``[2, kmax]`` (the last ``kmax`` inputs, double-buffered: a push reads one half and
+    writes the other), ``counts`` int64 ``[2]`` (inputs consumed, outputs emitted); ``count`` (a ``ResampleCount``,
+    the caller's when given) mirrors the two on the host, so no push reads the device back.  Output ``q`` lands in
+    ``ring[q % cap]``.  All pushes of one stream must be issued on one HIP stream."""
+
+    def __init__(self, sr_in: int, ring: torch.Tensor, sr_out: int = 16000, count: "ResampleCount" = None):
+        if not ring.is_cuda:
+            raise RuntimeError("ResampleStream runs on the MI355X kernels; keep the ring on the GPU")
+        if ring.dtype != torch.float32 or ring.dim() != 1 or not ring.is_contiguous() or ring.numel() < 1:
+            raise ValueError("the audio ring must be a contiguous fp32 [cap] tensor")
+        self.up, self.down = resample_ratio(sr_in, sr_out)
+        self.count = count if count is not None else ResampleCount(sr_in, sr_out)
+        if (self.count.up, self.count.down) != (self.up, self.down):
+            raise ValueError(f"the count given is for another rate than {sr_in} -> {sr_out}")
+        self.sr_in, self.ring, self.cap = int(sr_in), ring, int(ring.numel())
+        self.copy = self.up == 1 and self.down == 1
+        self.kmax = 0 if self.copy else 2 * 10 * max(self.up, self.down) // self.up + 1
+        if not self.copy and 255 * self.down // self.up + 1 + self.kmax > RESAMPLE_MAX_SPAN:
+            raise ValueError(f"sample rate {sr_in}: the resampler stages at most {RESAMPLE_MAX_SPAN} inputs per block")
+        dev = ring.device
+        self.table = None
+        if not self.copy:
+            key = (dev, self.up, self.down)
+            self.table = _POLYPHASE.get(key)
+            if self.table is None:
+                self.table = _POLYPHASE[key] = polyphase_table(self.up, self.down).to(dev)
+        self._hist = torch.zeros(2, max(self.kmax, 1), device=dev, dtype=torch.float32)
+        self.counts = torch.zeros(2, device=dev, dtype=torch.int64)
+        self._cur = 0
+
+    @property
+    def n_in(self) -> int:
+        return self.count.n_in
+
+    @property
+    def n_out(self) -> int:
+        return self.count.n_out
+
+    @property
+    def hist(self) -> torch.Tensor:
+        """The last ``kmax`` inputs (zeros before the stream start), oldest first."""
+        return self._hist[self._cur, :self.kmax]
+
+    def push(self, chunk: torch.Tensor) -> int:
+        """Feed the next inputs (1-D fp32, host or device); returns how many outputs this chunk emitted."""
+        flat = chunk.reshape(-1)
+        if flat.dtype != torch.float32:
+            raise ValueError("ResampleStream.push takes fp32 samples")
+        n = int(flat.numel())
+        if n == 0:
+            return 0
+        dev = self.ring.device
+        flat = flat.to(dev).contiguous() if flat.is_cuda else _h2d(flat.contiguous(), dev)
+        new = 1 - self._cur
+        K.LIB("mer_resample_stream", self.up, self.down, self.kmax, None if self.copy else self.table.data_ptr(),
+              flat.data_ptr(), n, self.n_in, None if self.copy else self._hist[self._cur].data_ptr(),
+              None if self.copy else self._hist[new].data_ptr(), self.kmax, self.ring.data_ptr(), self.cap,
+              self.counts.data_ptr(), K.stream_ptr())
+        self._cur = new
+        return self.count.advance(n)
 
 
 MEL_N_FFT, MEL_HOP, MEL_BINS, MEL_BINS_PAD = 400, 160, 201, 208

@@ -1405,3 +1405,60 @@ def timeline_smooth(probs: torch.Tensor, radius: int):
         LIB("mer_timeline_smooth", Nw, C, min(int(radius), Nw), probs.data_ptr(), smoothed.data_ptr(), top1.data_ptr(),
             stream_ptr())
     return smoothed, top1
+
+
+# ---- live streaming sessions (csrc/stream.hip) ----
+def rows_scatter(src: torch.Tensor, idx, dst: torch.Tensor) -> torch.Tensor:
+    """``dst[idx[r], :] = src[r, :]`` for fp32 rows on the GPU (bit-exact): mer_rows_scatter.  ``idx`` holds one
+    destination row per source row, every value in ``[0, dst.shape[0])`` and no value twice (two rows to one
+    destination would race): both are checked ON THE HOST, a bad index raises ``ValueError`` before any launch."""
+    if not src.is_cuda or not dst.is_cuda:
+        raise RuntimeError("rows_scatter runs on the MI355X kernels; move the rows to the GPU")
+    if src.dtype != torch.float32 or src.dim() != 2 or dst.dtype != torch.float32 or dst.dim() != 2 \
+            or dst.shape[1] != src.shape[1] or not dst.is_contiguous() or dst.device != src.device:
+        raise ValueError("rows_scatter takes fp32 rows src [R, D] and a contiguous fp32 dst [N, D] on one device")
+    src = src.contiguous()
+    R, D = src.shape
+    host = torch.as_tensor(idx)
+    host = host.cpu() if host.numel() else host.to(torch.int64).cpu()  # ONE host copy serves every check
+    dix = checked_index(host, dst.shape[0], src.device, "rows_scatter index")
+    if dix.numel() != R:
+        raise ValueError(f"rows_scatter: {dix.numel()} destinations for {R} rows")
+    if int(torch.unique(host).numel()) != R:
+        raise ValueError("rows_scatter index holds a destination row twice")
+    if R and D:
+        LIB("mer_rows_scatter", dst.shape[0], R, D, src.data_ptr(), dix.data_ptr(), dst.data_ptr(), stream_ptr())
+    return dst
+
+
+def ring_windows(rings: torch.Tensor, slot, end, count, target: int) -> torch.Tensor:
+    """The newest samples of ``B`` audio rings in one launch: ``rings`` fp32 ``[n_slots, cap]`` on the GPU ->
+    ``[B, 1, target]``, row ``b`` = the last ``min(count[b], cap, target)`` samples of ring ``slot[b]`` ending just
+    before position ``end[b]``, in time order across the wrap, then zeros (mer_ring_windows; the reference's crop from
+    the end / pad at the end, preprocess.py:319-323).  ``slot`` / ``end`` / ``count``: sequences or host int64 tensors
+    of one length, checked on the host (``ValueError`` before any launch): slots in ``[0, n_slots)``, ends in
+    ``[0, cap)``, counts >= 0 (a count above ``cap`` is a stream longer than its ring)."""
+    if not rings.is_cuda:
+        raise RuntimeError("ring_windows runs on the MI355X kernels; keep the rings on the GPU")
+    if rings.dtype != torch.float32 or rings.dim() != 2 or not rings.is_contiguous() or rings.shape[1] < 1:
+        raise ValueError("ring_windows takes contiguous fp32 rings [n_slots, cap]")
+    target = int(target)
+    if target <= 0:
+        raise ValueError(f"target must be positive, got {target}")
+    n_slots, cap = rings.shape
+    try:
+        meta = torch.stack([torch.as_tensor(v, dtype=torch.int64).reshape(-1).cpu() for v in (slot, end, count)])
+    except (RuntimeError, TypeError, ValueError):
+        raise ValueError("ring_windows: slot, end and count must be integer arrays of one length") from None
+    B = int(meta.shape[1])
+    if B > 65535:
+        raise ValueError(f"ring_windows serves at most 65535 sessions per launch, got {B}")
+    if B and (int(meta.min()) < 0 or int(meta[0].max()) >= n_slots or int(meta[1].max()) >= cap):
+        raise ValueError(f"ring_windows descriptor outside its range: slots in [0, {n_slots}), ends in [0, {cap}), "
+                         "counts >= 0")
+    out = torch.empty(B, 1, target, device=rings.device, dtype=torch.float32)
+    if B:
+        dmeta = meta.contiguous().pin_memory().to(rings.device, non_blocking=True)
+        LIB("mer_ring_windows", B, target, rings.data_ptr(), n_slots, cap, dmeta[0].data_ptr(), dmeta[1].data_ptr(),
+            dmeta[2].data_ptr(), out.data_ptr(), stream_ptr())
+    return out

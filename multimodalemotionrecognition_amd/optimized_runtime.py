@@ -232,6 +232,15 @@ class TorchModelRunner:
                 "window_seconds": float(window_sec)}
 
 
+    def open_stream_pool(self, max_sessions: int = 16, **kw):
+        """A ``streaming.StreamingSessionPool`` on this runner: live sessions whose audio, frames and frame features
+        stay in device rings, every sample resampled once, every frame encoded at most once, all due sessions
+        predicted in one batch.  GPU runners only (``RuntimeError`` otherwise)."""
+        from .streaming import StreamingSessionPool
+
+        return StreamingSessionPool(self, max_sessions, **kw)
+
+
 def _softmax(x: torch.Tensor) -> torch.Tensor:
     from . import kernels as K
 
