@@ -711,14 +711,27 @@ MER_API int mer_bn_bwd_apply2(long M, int C, const void* dy, const void* mask, c
 // ---------------------------------------------------------------------------------------
 // MaxPool2d(3, 2, 1) (resnet stem) channel-last, with the argmax tap (0..8) saved for backward.
 // ---------------------------------------------------------------------------------------
-// 8 channels (16 B) per thread; pixel index decomposed with fdiv (N*Ho*Wo < 2^22)
-__global__ void maxpool_fwd_kernel(int N, int H, int W, int C, int Ho, int Wo, const bf16_t* __restrict__ x,
-                                   bf16_t* __restrict__ y, uint8_t* __restrict__ arg) {
+// 8 channels (16 B) per thread.  The 16-byte-chunk index e = pixel * C/8 + chunk runs to N*H*W*C/8 < 2^30, far past
+// fdiv's exact range (common.h: it is first wrong at 2^23 + 7 for C/8 = 8), so the chunk split is an integer one -- a
+// shift where C/8 is a power of two (every trunk shape), a 32-bit divide otherwise -- and fdiv only decomposes the
+// pixel index, which the launchers keep below 2^22.
+__device__ __forceinline__ int chunk_div(int e, int cpr, int cpr_shift) {
+  return cpr_shift >= 0 ? e >> cpr_shift : e / cpr;
+}
+static int chunk_shift(int cpr) { return (cpr & (cpr - 1)) ? -1 : __builtin_ctz((unsigned)cpr); }
+// what the pooling launchers admit: pixels < 2^22 (fdiv, common.h) and chunks < 2^30 (32-bit e plus one grid stride)
+static bool pool_index_ok(int N, int H, int W, int C) {
+  const long pixels = (long)N * H * W;
+  return N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && pixels < (1L << 22) && pixels * (C / 8) < (1L << 30);
+}
+
+__global__ void maxpool_fwd_kernel(int N, int H, int W, int C, int Ho, int Wo, int cpr_shift,
+                                   const bf16_t* __restrict__ x, bf16_t* __restrict__ y, uint8_t* __restrict__ arg) {
   const int cpr = C / 8;
   const int total = N * Ho * Wo * cpr;
-  const float inv_cpr = 1.f / cpr, inv_Wo = 1.f / Wo, inv_Ho = 1.f / Ho;
+  const float inv_Wo = 1.f / Wo, inv_Ho = 1.f / Ho;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = fdiv(e, inv_cpr);
+    const int q = chunk_div(e, cpr, cpr_shift);  // output pixel, < N*H*W < 2^22: fdiv below is exact
     const int c0 = (e - q * cpr) * 8;
     const int q2 = fdiv(q, inv_Wo);
     const int ow = q - q2 * Wo;
@@ -752,21 +765,22 @@ __global__ void maxpool_fwd_kernel(int N, int H, int W, int C, int Ho, int Wo, c
 }
 MER_API int mer_maxpool_fwd(int N, int H, int W, int C, const void* x, void* y, void* argmax, void* stream) {
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
+  if (!pool_index_ok(N, H, W, C)) return (int)hipErrorInvalidValue;
   const long total = (long)N * Ho * Wo * C / 8;
   const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, N, H, W, C, Ho, Wo,
-                     (const bf16_t*)x, (bf16_t*)y, (uint8_t*)argmax);
+                     chunk_shift(C / 8), (const bf16_t*)x, (bf16_t*)y, (uint8_t*)argmax);
   MER_LAUNCH_CHECK();
 }
 // gather backward: dx[n,h,w,c] = sum of dy over the (<= 4) windows whose argmax is (h,w)
-__global__ void maxpool_bwd_kernel(int N, int H, int W, int C, int Ho, int Wo, const bf16_t* __restrict__ dy,
-                                   const uint8_t* __restrict__ arg, bf16_t* __restrict__ dx) {
+__global__ void maxpool_bwd_kernel(int N, int H, int W, int C, int Ho, int Wo, int cpr_shift,
+                                   const bf16_t* __restrict__ dy, const uint8_t* __restrict__ arg,
+                                   bf16_t* __restrict__ dx) {
   const int cpr = C / 8;
   const int total = N * H * W * cpr;
-  const float inv_cpr = 1.f / cpr, inv_W = 1.f / W, inv_H = 1.f / H;
+  const float inv_W = 1.f / W, inv_H = 1.f / H;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = fdiv(e, inv_cpr);
+    const int q = chunk_div(e, cpr, cpr_shift);  // (pixel q < 2^22: fdiv below is exact)
     const int c0 = (e - q * cpr) * 8;
     const int q2 = fdiv(q, inv_W);
     const int w = q - q2 * W;
@@ -810,11 +824,11 @@ __global__ void maxpool_bwd_kernel(int N, int H, int W, int C, int Ho, int Wo, c
 }
 MER_API int mer_maxpool_bwd(int N, int H, int W, int C, const void* dy, const void* argmax, void* dx, void* stream) {
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
+  if (!pool_index_ok(N, H, W, C)) return (int)hipErrorInvalidValue;
   const long total = (long)N * H * W * C / 8;
   const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, N, H, W, C, Ho, Wo,
-                     (const bf16_t*)dy, (const uint8_t*)argmax, (bf16_t*)dx);
+                     chunk_shift(C / 8), (const bf16_t*)dy, (const uint8_t*)argmax, (bf16_t*)dx);
   MER_LAUNCH_CHECK();
 }
 
@@ -827,15 +841,15 @@ MER_API int mer_maxpool_bwd(int N, int H, int W, int C, const void* dy, const vo
 // Same roundings, tap order and tie rule as bn_apply -> maxpool_fwd / maxpool_bwd -> bn_bwd_*.
 // ---------------------------------------------------------------------------------------
 
-__global__ void stem_bnrelu_maxpool_kernel(int N, int H, int W, int C, int Ho, int Wo, const bf16_t* __restrict__ x,
-                                           const float* __restrict__ ms, const float* __restrict__ gamma,
-                                           const float* __restrict__ beta, bf16_t* __restrict__ y,
-                                           uint8_t* __restrict__ arg) {
+__global__ void stem_bnrelu_maxpool_kernel(int N, int H, int W, int C, int Ho, int Wo, int cpr_shift,
+                                           const bf16_t* __restrict__ x, const float* __restrict__ ms,
+                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                           bf16_t* __restrict__ y, uint8_t* __restrict__ arg) {
   const int cpr = C / 8;
   const int total = N * Ho * Wo * cpr;
-  const float inv_cpr = 1.f / cpr, inv_Wo = 1.f / Wo, inv_Ho = 1.f / Ho;
+  const float inv_Wo = 1.f / Wo, inv_Ho = 1.f / Ho;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int q = fdiv(e, inv_cpr);
+    const int q = chunk_div(e, cpr, cpr_shift);  // (as maxpool_fwd_kernel)
     const int c0 = (e - q * cpr) * 8;
     const int q2 = fdiv(q, inv_Wo);
     const int ow = q - q2 * Wo;
@@ -883,18 +897,18 @@ __global__ void stem_bnrelu_maxpool_kernel(int N, int H, int W, int C, int Ho, i
 MER_API int mer_stem_bnrelu_maxpool_fwd(int N, int H, int W, int C, const void* x, const float* ms, const float* gamma,
                                         const float* beta, void* y, void* argmax, void* stream) {
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || C > 512 || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
+  if (C > 512 || !pool_index_ok(N, H, W, C)) return (int)hipErrorInvalidValue;
   const long total = (long)N * Ho * Wo * C / 8;
   const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(stem_bnrelu_maxpool_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, N, H, W, C, Ho, Wo,
-                     (const bf16_t*)x, ms, gamma, beta, (bf16_t*)y, (uint8_t*)argmax);
+                     chunk_shift(C / 8), (const bf16_t*)x, ms, gamma, beta, (bf16_t*)y, (uint8_t*)argmax);
   MER_LAUNCH_CHECK();
 }
 
 MER_API int mer_stem_pool_bn_bwd(int N, int H, int W, int C, const void* dy, const void* argmax, const void* x,
                                  const float* ms, const float* gamma, const float* beta, float* red, int batch_stats,
                                  void* dx, float* dgamma, float* dbeta, float* workspace, void* stream) {
-  if (C % 8 || C > 512 || 256 % (C / 8) || (long)N * H * W >= (1L << 22)) return (int)hipErrorInvalidValue;
+  if (C > 512 || !pool_index_ok(N, H, W, C) || 256 % (C / 8)) return (int)hipErrorInvalidValue;
   const hipStream_t st = (hipStream_t)stream;
   const long M = (long)N * H * W;
   // 1) maxpool gather backward into dx (as the pre-BN gradient); 2) BN reduction with the ReLU mask

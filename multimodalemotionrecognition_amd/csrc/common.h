@@ -123,7 +123,12 @@ __device__ __forceinline__ void dropout_pairs(float* v, uint64_t seed, uint64_t 
 
 // a / d for 0 <= a < 2^22 with inv_d = 1.0f / d (d >= 1): exact, ~3 VALU ops instead of an
 // integer-division sequence.  (a + 0.5) / d sits >= 0.5/d away from any integer, far more than the
-// float rounding error at these magnitudes.
+// float rounding error at these magnitudes.  Past 2^22 it is NOT exact (d = 8: a = 2^23 + 7 and every later
+// a = 7 mod 8 give q + 1; d = 3, 7, 28, 56, 112 fail near 1.5 * 2^22; tests/test_kernel_parity_cpu.py emulates it), so
+// every caller bounds the operand itself: K indices and tap counts in the convs (conv_wgrad.hip also an output-pixel
+// index, 802,816 at most today), s2d pixels chunked below 2^22 on the host, and in bn_pool.hip the PIXEL index only
+// (launch guard pool_index_ok: N*H*W < 2^22) -- the 16-byte-chunk index there is C/8 times larger and is split with
+// an integer shift / divide (chunk_div).
 __device__ __forceinline__ int fdiv(int a, float inv_d) { return (int)(((float)a + 0.5f) * inv_d); }
 
 // XCD-aware tile order (cdna_hip_programming.md T1, bijective form): blocks are dealt round-robin over

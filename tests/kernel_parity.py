@@ -1,9 +1,10 @@
-"""Direct parity of single fp32 kernels against float64 restatements (a plain helper module, not a conftest).
+"""Direct parity of single kernels against float64 restatements (a plain helper module, not a conftest).
 
 Every restatement below is the operation written in plain torch on the CPU, evaluated in the dtype ``dt`` it is given:
 float64 is the reference, float32 the same text in the kernels' precision.  ``assert_fp64_parity`` bounds a kernel's
 error by 16 x the error of the float32 restatement: the bar is measured against the reference,
-never against the kernel.
+never against the kernel.  A kernel that stores bfloat16 meets ``assert_bf16_parity``: the same bar, with the final
+rounding applied to the reference's interval instead of a bf16 tolerance.
 
 Scalars that cross the C ABI as ``float`` (dropout p, LayerNorm eps, the softmax scale, Adam's hyper-parameters) are
 rounded to float32 before either restatement uses them: ``0.999f != 0.999`` is not a kernel error.
@@ -49,6 +50,69 @@ def assert_fp64_parity(got, ref64, ref32, extra=0.0, what=""):
 def assert_parity_all(got: dict, ref64: dict, ref32: dict, keys, extra=None, what=""):
     for k in keys:
         assert_fp64_parity(got[k], ref64[k], ref32[k], extra=(extra or {}).get(k, 0.0), what=f"{what} {k}")
+
+
+BF16 = torch.bfloat16
+
+
+def to_bf16(t) -> torch.Tensor:
+    """Round to bfloat16 the way the comparison below means it: float64 -> float32 -> bfloat16, both to nearest even
+    (torch converts float64 to bfloat16 through float32 anyway: 1 + 2^-8 + 2^-30 becomes 1.0)."""
+    return t.to(F32).to(BF16)
+
+
+def bf16_interval(ref64, ref32):
+    """(lo, hi, tol): the bfloat16 values a kernel that stores bf16 may return, as float64 tensors.
+    tol = 16 max|ref32 - ref64| + eps32 max|ref64| is the float32 bar of assert_fp64_parity; lo / hi are the bf16
+    roundings of ref64 -/+ tol."""
+    assert ref64.dtype == F64 and ref32.dtype == F32 and tuple(ref64.shape) == tuple(ref32.shape)
+    tol = 16.0 * _max_abs(ref32.to(F64) - ref64) + EPS32 * _max_abs(ref64)
+    return to_bf16(ref64 - tol).to(F64), to_bf16(ref64 + tol).to(F64), tol
+
+
+def bf16_determined(lo, hi, tol):
+    """Elements at which the interval says as much as the float32 bar does: no bf16 rounding boundary within tol of
+    the reference (lo == hi: the kernel's bits are fixed), or bf16 itself finer than the bar there (hi - lo no wider
+    than 2 tol rounded outwards: the exact zeros of a ReLU, of a masked gradient, of the pixels no pooling window
+    selects).  Elsewhere the interval spans a whole bf16 step, thousands of times tol."""
+    return (hi - lo) <= 2 * tol * (1 + 2.0 ** -7)
+
+
+def assert_bf16_parity(got, ref64, ref32, what="", min_determined=0.9):
+    """A kernel that stores bfloat16: every element must be the bf16 rounding of something within the float32 bar of
+    the reference, bf16(ref64 - tol) <= got <= bf16(ref64 + tol) with tol = 16 max|ref32 - ref64| + eps32 max|ref64|.
+    ``ref64`` / ``ref32`` are the restatement before its final rounding.  No bf16 tolerance appears: where no rounding
+    boundary lies within tol of the reference (lo == hi, "determined") the kernel's bits are fixed; an element where
+    bf16 is finer than tol (an exact zero) counts as determined too, see bf16_determined.  The eps32 term
+    also covers the float32 step of the float64 -> bfloat16 conversion.  At least ``min_determined`` of the elements
+    must be determined, else the check is blind; that is a condition on the inputs, not on the kernel
+    (tests/test_kernel_parity_cpu.py shows the restatements meet it).  Prints and returns err / bar like
+    assert_fp64_parity, with err the largest distance from ref64 at which a value rounds to the kernel's bf16 (0 where
+    got == bf16(ref64))."""
+    got = torch.as_tensor(got).detach().cpu()
+    assert got.dtype == BF16, f"{what}: expected a bfloat16 output, got {got.dtype}"
+    assert tuple(got.shape) == tuple(ref64.shape), (what, got.shape, ref64.shape)
+    lo, hi, tol = bf16_interval(ref64, ref32)
+    det = bf16_determined(lo, hi, tol)
+    share = float(det.double().mean()) if det.numel() else 1.0
+    assert share >= min_determined, f"{what}: only {share:.1%} of the elements are determined, the check is blind"
+    g = got.to(F64)
+    assert bool(torch.isfinite(g).all()), f"{what}: non-finite kernel output (or an element never written)"
+    # err: how far from ref64 the value the kernel rounded must have been -- 0 where got is bf16(ref64), else the
+    # distance from ref64 to the rounding boundary between the two (their midpoint); this is what tol bounds
+    r = to_bf16(ref64).to(F64)
+    err = _max_abs(torch.where(g != r, (g + r) / 2 - ref64, torch.zeros_like(g)))
+    bar = _max_abs(ref32.to(F64) - ref64)
+    ratio = err / bar if bar > 0 else (0.0 if err == 0 else math.inf)
+    print(f"parity {what}: err={err:.3e} bar={bar:.3e} ratio={ratio:.3f} determined={share:.3f} tol={tol:.3e}")
+    bad = (g < lo) | (g > hi)
+    if bool(bad.any()):
+        i = int(bad.reshape(-1).nonzero()[0])
+        at = [float(t.reshape(-1)[i]) for t in (g, lo, hi, ref64)]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bf16 interval; first at "
+                             f"flat index {i}: got {at[0]!r}, interval [{at[1]!r}, {at[2]!r}], ref64 {at[3]!r}, "
+                             f"tol {tol:.3e}")
+    return ratio
 
 
 # ---- dropout masks restated on the host (tests/helpers.dropout_keep) ----
@@ -139,6 +203,34 @@ def padded_input(t, strides, device, offset=0):
 
 def padded_rows(t, pad, device, offset=0):
     return padded_input(t, (t.shape[1] + pad, 1), device, offset)
+
+
+class GuardedBf16:
+    """A contiguous bfloat16 (or uint8) output of ``shape`` inside a longer flat buffer.  MARKER is not a bf16 value,
+    so the buffer is pre-filled with NaN (0xFF bytes for uint8): ``check`` requires every element in front of and
+    behind the view to keep its bits and every element of the view to have been written.  The view starts 16 elements
+    in, so 16-byte vector stores stay aligned."""
+
+    def __init__(self, shape, device, dtype=BF16, pad=16):
+        n = int(np.prod(shape))
+        self.fill = 0xFF if dtype == torch.uint8 else float("nan")
+        self.buf = torch.full((pad + n + pad,), self.fill, dtype=dtype, device=device)
+        self.view = self.buf[pad:pad + n].view(tuple(shape))
+        self.pad, self.n = pad, n
+
+    def _untouched(self, t):
+        return bool((t == 0xFF).all()) if t.dtype == torch.uint8 else bool(torch.isnan(t).all())
+
+    def check(self, what="", written=True):
+        b = self.buf.detach().cpu()
+        assert self._untouched(b[:self.pad]) and self._untouched(b[self.pad + self.n:]), \
+            f"{what}: elements outside the output view were overwritten"
+        v = b[self.pad:self.pad + self.n]
+        if written:
+            never = (v == 0xFF) if v.dtype == torch.uint8 else torch.isnan(v)
+            assert not bool(never.any()), f"{what}: {int(never.sum())} output elements never written"
+        if not written:
+            assert self._untouched(v), f"{what}: the output was written by a call that must refuse"
 
 
 # ---- seeded CPU inputs ----
@@ -297,6 +389,140 @@ def ref_clip_align(a, v, log_scale, dloss, dls0, dt):
     return {k: t.detach() for k, t in out.items()}
 
 
+# ---- csrc/bn_pool.hip: BatchNorm and pooling of the video trunk (channel-last, bf16 activations) ----
+def bf16_values(g, *shape, scale=1.0, shift=0.0):
+    """Seeded float32 values that are exactly representable in bfloat16 (the kernels' inputs, widened)."""
+    return to_bf16(randn(g, *shape) * scale + shift).to(F32)
+
+
+def tile_stats(x):
+    """Conv-epilogue statistics rows of a bf16-valued x[M, C]: per 64-row tile (sum, sum of squares), accumulated in
+    float64 and rounded to float32 -> [ceil(M / 64), C, 2]."""
+    M, C = x.shape
+    rows = (M + 63) // 64
+    xp = torch.zeros(rows * 64, C, dtype=F64)
+    xp[:M] = x.to(F64)
+    xp = xp.view(rows, 64, C)
+    return torch.stack([xp.sum(1), (xp * xp).sum(1)], -1).to(F32)
+
+
+def ref_bn_finalize(stats, M, eps, momentum, rmean, rvar, dt):
+    """Train form: ``stats`` [rows, C, 2] partial (sum, sumsq) rows -> mean, rstd = 1 / sqrt(max(var, 0) + eps), and
+    the running statistics with the unbiased variance M / (M - 1) (factor 1 at M = 1).  Eval form (``stats`` None):
+    the running statistics copied / inverted, nothing updated.  num_batches_tracked (+1 in the train form) is an
+    integer and is asserted by the caller."""
+    eps_t, mom = torch.tensor(f32(eps), dtype=dt), torch.tensor(f32(momentum), dtype=dt)
+    if stats is None:
+        return {"mean": rmean.to(dt).clone(), "rstd": 1 / torch.sqrt(rvar.to(dt) + eps_t)}
+    tot = stats.to(dt).sum(0)
+    Mt = torch.tensor(float(M), dtype=dt)
+    mean = tot[:, 0] / Mt
+    var = torch.clamp(tot[:, 1] / Mt - mean * mean, min=0)
+    out = {"mean": mean, "rstd": 1 / torch.sqrt(var + eps_t)}
+    if rmean is not None:
+        out["rmean"] = (1 - mom) * rmean.to(dt) + mom * mean
+    if rvar is not None:
+        unbias = Mt / torch.tensor(float(M - 1 if M > 1 else 1), dtype=dt)
+        out["rvar"] = (1 - mom) * rvar.to(dt) + mom * var * unbias
+    return out
+
+
+def _bn_fold(ms, gamma, beta, dt):
+    """BatchNorm as one (scale, shift) per channel, the form the kernels document: scale = rstd gamma,
+    shift = beta - mean scale."""
+    ms = ms.to(dt)
+    scale = ms[:, 1] * gamma.to(dt)
+    return scale, beta.to(dt) - ms[:, 0] * scale
+
+
+def ref_bn_apply(x, ms, gamma, beta, relu, dt, res=None, ms2=None, gamma2=None, beta2=None):
+    """y = [relu](bn(x) + r) before its bf16 rounding; r: nothing, the raw residual, or bn2(res)."""
+    scale, shift = _bn_fold(ms, gamma, beta, dt)
+    y = x.to(dt) * scale + shift
+    if res is not None:
+        if ms2 is not None:
+            scale2, shift2 = _bn_fold(ms2, gamma2, beta2, dt)
+            y = y + (res.to(dt) * scale2 + shift2)
+        else:
+            y = y + res.to(dt)
+    return {"y": torch.relu(y) if relu else y}
+
+
+def ref_bn_bwd(dy, mask, x, ms, gamma, batch_stats, dt, red=None, dgamma0=None, dbeta0=None):
+    """g = dy (mask > 0); red = (sum g, sum g xhat); dx = gamma rstd (g - sum g / M - xhat sum g xhat / M) with batch
+    statistics, gamma rstd g without; dgamma / dbeta accumulate onto their start values.  ``red`` given: dx, dgamma
+    and dbeta use it instead of the sums (the apply kernel judged alone)."""
+    C, shape = x.shape[-1], x.shape
+    dy, x, ms = dy.to(dt).reshape(-1, C), x.to(dt).reshape(-1, C), ms.to(dt)
+    M = x.shape[0]
+    g = dy if mask is None else torch.where(mask.reshape(-1, C) > 0, dy, torch.zeros((), dtype=dt))
+    mean, rstd = ms[:, 0], ms[:, 1]
+    xhat = (x - mean) * rstd
+    sums = torch.stack([g.sum(0), (g * xhat).sum(0)], -1)
+    use = sums if red is None else red.to(dt)
+    k = gamma.to(dt) * rstd
+    dx = k * (g - use[:, 0] / M - xhat * (use[:, 1] / M)) if batch_stats else k * g
+    zero = torch.zeros(C, dtype=dt)
+    return {"red": sums, "dx": dx.reshape(shape), "dgamma": (zero if dgamma0 is None else dgamma0.to(dt)) + use[:, 1],
+            "dbeta": (zero if dbeta0 is None else dbeta0.to(dt)) + use[:, 0]}
+
+
+def maxpool_out(n):
+    return (n + 2 - 3) // 2 + 1
+
+
+def maxpool_taps(xp, Ho, Wo):
+    """3x3 / stride-2 max over an already padded [N, >= 2 Ho + 1, >= 2 Wo + 1, C] tensor (-inf outside the frame):
+    nine shifted comparisons in tap order t = 3 r + s, a later tap wins only when strictly greater -- the argmax is
+    the FIRST maximum (0 when every tap is -inf)."""
+    best = torch.full((xp.shape[0], Ho, Wo, xp.shape[3]), -math.inf, dtype=xp.dtype)
+    arg = torch.zeros(best.shape, dtype=torch.uint8)
+    for t in range(9):
+        r, s = divmod(t, 3)
+        v = xp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2]
+        up = v > best
+        best = torch.where(up, v, best)
+        arg = torch.where(up, torch.full((), t, dtype=torch.uint8), arg)
+    return best, arg
+
+
+def ref_maxpool(x, dy, dt, arg=None):
+    """MaxPool2d(3, 2, 1) on [N, H, W, C]: y, the argmax tap, and dx = dy gathered through the argmax (``arg`` given:
+    through that one; a tap that points outside the frame receives nothing)."""
+    N, H, W, C = x.shape
+    Ho, Wo = maxpool_out(H), maxpool_out(W)
+    xp = torch.full((N, H + 2, W + 2, C), -math.inf, dtype=dt)
+    xp[:, 1:H + 1, 1:W + 1] = x.to(dt)
+    y, amax = maxpool_taps(xp, Ho, Wo)
+    out = {"y": y, "arg": amax.to(dt)}
+    if dy is not None:
+        out["dx"] = maxpool_gather(dy, amax if arg is None else arg, H, W, dt)
+    return out
+
+
+def maxpool_gather(dy, arg, H, W, dt):
+    N, Ho, Wo, C = dy.shape
+    dxp = torch.zeros(N, H + 2, W + 2, C, dtype=dt)
+    dy = dy.to(dt)
+    for t in range(9):
+        r, s = divmod(t, 3)
+        dxp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += torch.where(arg == t, dy, torch.zeros((), dtype=dt))
+    return dxp[:, 1:H + 1, 1:W + 1].contiguous()
+
+
+def ref_avgpool(x, dy, dt):
+    """Global average pool [N, H, W, C] -> [N, C] and its backward dx = dy / HW (before the bf16 rounding)."""
+    N, H, W, C = x.shape
+    HW = H * W
+    return {"y": x.to(dt).sum((1, 2)) / HW, "dx": (dy.to(dt) / HW)[:, None, None, :].expand(N, H, W, C).contiguous()}
+
+
+def ref_rows_sum(rows, out0, dt):
+    """out = out0 + sum over the leading dimension (the partial-row folds)."""
+    tot = rows.to(dt).sum(0)
+    return {"out": tot if out0 is None else out0.to(dt) + tot}
+
+
 # ======================================================================================================
 # One small seeded instance of every restatement (tests/test_kernel_parity_cpu.py checks that its float32
 # evaluation is a non-degenerate bar).  name -> fn(dt) -> dict of outputs.
@@ -369,10 +595,42 @@ def _instances():
     ca, cv = randn(g, 5, 70), randn(g, 5, 70)
     ls, dl, dls0 = torch.tensor([math.log(1 / 0.07)]), torch.tensor([0.7]), torch.tensor([0.25])
     inst["clip_align"] = lambda dt: ref_clip_align(ca, cv, ls, dl, dls0, dt)
+    # csrc/bn_pool.hip
+    gb = gen(20261021)
+    C, M = 24, 200
+    xb = bf16_values(gb, M, C, shift=0.5)
+    st = tile_stats(xb)
+    rm0, rv0 = randn(gb, C) * 0.1, torch.rand(C, generator=gb) + 0.5
+    inst["bn_finalize"] = lambda dt: ref_bn_finalize(st, M, 1e-5, 0.1, rm0, rv0, dt)
+    inst["bn_finalize_eval"] = lambda dt: ref_bn_finalize(None, M, 1e-5, 0.1, rm0, rv0, dt)
+    ms_b = torch.stack([xb.mean(0), 1 / torch.sqrt(xb.var(0, unbiased=False) + 1e-5)], 1)
+    ms_r = torch.stack([randn(gb, C) * 0.2, torch.rand(C, generator=gb) + 0.5], 1)
+    ga, be, ga2, be2 = torch.rand(C, generator=gb) + 0.5, randn(gb, C) * 0.2, torch.rand(C, generator=gb) + 0.5, \
+        randn(gb, C) * 0.2
+    rb = bf16_values(gb, M, C)
+    inst["bn_apply"] = lambda dt: ref_bn_apply(xb, ms_b, ga, be, False, dt)
+    inst["bn_apply_res_relu"] = lambda dt: ref_bn_apply(xb, ms_b, ga, be, True, dt, res=rb)
+    inst["bn_apply_resbn_relu"] = lambda dt: ref_bn_apply(xb, ms_b, ga, be, True, dt, res=rb, ms2=ms_r, gamma2=ga2,
+                                                          beta2=be2)
+    dyb, mk = bf16_values(gb, M, C), torch.relu(bf16_values(gb, M, C))
+    dg0, db0 = randn(gb, C), randn(gb, C)
+    inst["bn_bwd"] = lambda dt: ref_bn_bwd(dyb, mk, xb, ms_b, ga, True, dt, dgamma0=dg0, dbeta0=db0)
+    inst["bn_bwd_running"] = lambda dt: ref_bn_bwd(dyb, None, xb, ms_b, ga, False, dt, dgamma0=dg0, dbeta0=db0)
+    xp_, dyp = bf16_values(gb, 2, 9, 7, 8), bf16_values(gb, 2, 5, 4, 8)
+    inst["maxpool"] = lambda dt: ref_maxpool(xp_, dyp, dt)
+    dya = randn(gb, 2, 8)
+    inst["avgpool"] = lambda dt: ref_avgpool(xp_, dya, dt)
+    pr, o0 = randn(gb, 65, 40), randn(gb, 40)
+    inst["rows_sum"] = lambda dt: ref_rows_sum(pr, o0, dt)
     return inst
 
 
 INSTANCES = _instances()
 # Outputs that are copies of an input in any precision (no arithmetic): their bar is zero by construction and only
-# the one-ulp floor of assert_fp64_parity applies.  Without a residual the saved pre-norm sum is x itself.
-EXACT_OUTPUTS = {"add_ln_no_r": {"s"}}
+# the one-ulp floor of assert_fp64_parity applies.  Without a residual the saved pre-norm sum is x itself; the max
+# pool's y and argmax and the eval-mode BatchNorm mean are copies; the max pool's dx adds at most four bf16 values of
+# one scale, which float32 does exactly.
+EXACT_OUTPUTS = {"add_ln_no_r": {"s"}, "maxpool": {"y", "arg", "dx"}, "bn_finalize_eval": {"mean"}}
+# Outputs the kernels store as bfloat16: judged by assert_bf16_parity.
+BF16_OUTPUTS = {"bn_apply": {"y"}, "bn_apply_res_relu": {"y"}, "bn_apply_resbn_relu": {"y"}, "bn_bwd": {"dx"},
+                "bn_bwd_running": {"dx"}, "maxpool": {"y", "dx"}, "avgpool": {"dx"}}

@@ -1,5 +1,9 @@
-"""The bars of tests/test_head_kernels_gpu.py are sound: every float32 restatement is close to, and distinct from,
-its float64 reference, and ``assert_fp64_parity`` accepts the former and rejects a 1e-4 perturbation of it."""
+"""The bars of tests/test_head_kernels_gpu.py and tests/test_bn_pool_kernels_gpu.py are sound: every float32
+restatement is close to, and distinct from, its float64 reference, and ``assert_fp64_parity`` accepts the former and
+rejects a 1e-4 perturbation of it.  ``assert_bf16_parity`` accepts bf16(ref32), rejects one bf16 step of a determined
+element and anything outside the interval, and finds at least 90 % of every bf16 output determined.  The max pool's
+restatement takes the first maximum; csrc/common.h ``fdiv``, emulated in float32, is exact below 2^22 and first wrong
+at 2^23 + 7 for a divisor of 8."""
 import numpy as np
 import pytest
 import torch
@@ -82,3 +86,135 @@ def test_guarded_view_detects_a_write_outside_it():
     f.buf[-1] = kp.MARKER + 1
     with pytest.raises(AssertionError):
         f.check()
+
+
+# ---- bfloat16 outputs: the interval rule of assert_bf16_parity ----
+BF16_CASES = sorted((n, k) for n, ks in kp.BF16_OUTPUTS.items() for k in ks)
+
+
+def _bf16_step(t, i, ulps):
+    """t (bfloat16) with element i moved by ``ulps`` representable values away from zero (towards it if negative)."""
+    bits = t.clone().reshape(-1).view(torch.int16)
+    bits[i] += ulps
+    return bits.view(torch.bfloat16).reshape(t.shape)
+
+
+@pytest.mark.parametrize("name,key", BF16_CASES)
+def test_assert_bf16_parity_on_every_bf16_output(name, key, evaluated, capsys):
+    ref64, ref32 = evaluated[name][0][key], evaluated[name][1][key]
+    got = kp.to_bf16(ref32)
+    kp.assert_bf16_parity(got, ref64, ref32, what=f"{name}.{key}")  # includes the 90 % determined-share condition
+    line = capsys.readouterr().out.strip().splitlines()[-1]
+    assert f"{name}.{key}" in line and "err=" in line and "bar=" in line and "ratio=" in line
+    lo, hi, tol = kp.bf16_interval(ref64, ref32)
+    assert tol <= 1e-4 * float(ref64.abs().max())
+    assert bool(((lo == hi) <= kp.bf16_determined(lo, hi, tol)).all())
+    det = (lo == hi).reshape(-1).nonzero().reshape(-1)
+    i = int(det[int(np.random.default_rng(len(name)).integers(det.numel()))])
+    for ulps in (1, -1):  # one bf16 step of one determined element, either way
+        with pytest.raises(AssertionError, match="outside the bf16 interval"):
+            kp.assert_bf16_parity(_bf16_step(got, i, ulps), ref64, ref32, what=f"{name}.{key} one ulp")
+    zeros = (ref64 == 0).reshape(-1).nonzero().reshape(-1)
+    if zeros.numel():  # an exact zero is determined although lo < hi: it admits nothing beyond tol
+        assert bool(kp.bf16_determined(lo, hi, tol).reshape(-1)[zeros].all())
+        assert float(hi.reshape(-1)[zeros[0]]) <= 1.01 * tol
+        bad = got.clone().reshape(-1)
+        bad[int(zeros[0])] = 1.05 * tol
+        with pytest.raises(AssertionError, match="outside the bf16 interval"):
+            kp.assert_bf16_parity(bad.reshape(got.shape), ref64, ref32, what=f"{name}.{key} non-zero")
+    for v in (float("nan"), float("inf")):
+        bad = got.clone().reshape(-1)
+        bad[i] = v
+        with pytest.raises(AssertionError):
+            kp.assert_bf16_parity(bad.reshape(got.shape), ref64, ref32, what=f"{name}.{key} {v}")
+
+
+def test_assert_bf16_parity_at_a_rounding_boundary():
+    """An element whose reference sits on a bf16 rounding boundary admits both neighbours and nothing beyond them; a
+    tensor with too many such elements is refused as blind."""
+    ref64 = torch.tensor([1.0 + 2.0 ** -8] + [1.001 + 2.0 ** -7 * k for k in range(19)], dtype=torch.float64)
+    ref32 = (ref64 + 1e-7).float()  # bar ~ 1e-7: tol ~ 1.7e-6, far below the bf16 step 2^-7
+    lo, hi, tol = kp.bf16_interval(ref64, ref32)
+    assert 1e-6 < tol < 3e-6
+    assert float(lo[0]) == 1.0 and float(hi[0]) == 1.0 + 2.0 ** -7 and bool((lo[1:] == hi[1:]).all())
+    ok = kp.to_bf16(ref64)
+    for v in (1.0, 1.0 + 2.0 ** -7):
+        ok[0] = v
+        kp.assert_bf16_parity(ok, ref64, ref32, what="boundary")
+    for v in (1.0 - 2.0 ** -8, 1.0 + 2.0 ** -6):  # just outside: the next bf16 value on either side
+        bad = ok.clone()
+        bad[0] = v
+        with pytest.raises(AssertionError, match="outside the bf16 interval"):
+            kp.assert_bf16_parity(bad, ref64, ref32, what="boundary")
+    with pytest.raises(AssertionError, match="blind"):
+        kp.assert_bf16_parity(ok[:5], ref64[:5], ref32[:5], what="one in five undetermined")
+    with pytest.raises(AssertionError, match="bfloat16"):
+        kp.assert_bf16_parity(ok.float(), ref64, ref32, what="float32 output")
+    # float64 -> bfloat16 goes through float32: the eps32 term of tol covers that step
+    assert float(torch.tensor(1 + 2.0 ** -8 + 2.0 ** -30, dtype=torch.float64).to(torch.bfloat16)) == 1.0
+    assert float(kp.to_bf16(torch.tensor(1 + 2.0 ** -8 + 2.0 ** -30, dtype=torch.float64))) == 1.0
+
+
+def test_guarded_bf16_detects_unwritten_and_outside_writes():
+    for dtype in (torch.bfloat16, torch.uint8):
+        g = kp.GuardedBf16((2, 3), "cpu", dtype=dtype)
+        g.check("refused call", written=False)
+        g.view.fill_(1)
+        g.check("written")
+        with pytest.raises(AssertionError, match="must refuse"):
+            g.check("refused call", written=False)
+        g.buf[-1] = 0
+        with pytest.raises(AssertionError, match="outside the output view"):
+            g.check("tail write")
+    g = kp.GuardedBf16((2, 3), "cpu")
+    g.view[0].fill_(1.0)
+    with pytest.raises(AssertionError, match="never written"):
+        g.check("half written")
+
+
+def test_ref_maxpool_takes_the_first_maximum_in_tap_order():
+    x = torch.tensor([[1., 5., 5.], [5., 2., 5.], [0., 5., 1.]]).reshape(1, 3, 3, 1)
+    dy = torch.tensor([[1., 2.], [4., 8.]]).reshape(1, 2, 2, 1)
+    for dt in (kp.F64, kp.F32):
+        o = kp.ref_maxpool(x, dy, dt)
+        assert o["y"].reshape(2, 2).tolist() == [[5., 5.], [5., 5.]]
+        # window (0,0) sees taps 4, 5, 7, 8 = 1, 5, 5, 2; (0,1) taps 3, 4, 6, 7 = 5, 5, 2, 5; (1,0) taps 1, 2, 4, 5 =
+        # 5, 2, 0, 5; (1,1) taps 0, 1, 3, 4 = 2, 5, 5, 1: the first 5 of each
+        assert o["arg"].reshape(2, 2).tolist() == [[5., 3.], [1., 1.]]
+        assert o["dx"].reshape(3, 3).tolist() == [[0., 3., 0.], [4., 0., 8.], [0., 0., 0.]]
+    lone = kp.ref_maxpool(torch.full((1, 1, 1, 1), -np.inf), torch.ones(1, 1, 1, 1), kp.F64)
+    assert float(lone["y"]) == -np.inf and float(lone["arg"]) == 0 and float(lone["dx"]) == 0  # tap 0 is off the frame
+    # a given argmax replaces the computed one; a tap outside the frame receives nothing
+    arg = torch.tensor([[0, 7], [4, 4]], dtype=torch.uint8).reshape(1, 2, 2, 1)
+    o = kp.ref_maxpool(x, dy, kp.F64, arg=arg)
+    assert o["dx"].reshape(3, 3).tolist() == [[0., 0., 0.], [0., 0., 2.], [4., 0., 8.]]
+    arg[0, 0, 1, 0] = 8  # (row 1, column 3) of a 3-wide frame
+    assert kp.ref_maxpool(x, dy, kp.F64, arg=arg)["dx"].reshape(3, 3).tolist() == [[0.] * 3, [0.] * 3, [4., 0., 8.]]
+
+
+# ---- csrc/common.h fdiv, emulated in float32: why the pooling kernels may not split their chunk index with it ----
+def fdiv_emulated(a, d):
+    inv = np.float32(1.0) / np.float32(d)
+    return ((a.astype(np.float32) + np.float32(0.5)) * inv).astype(np.int64)
+
+
+FDIV_DIVISORS = sorted(set(range(1, 65)) | {72, 112, 224, 515, 592, 600, 1030, 3136, 12544})
+
+
+def test_fdiv_is_exact_below_2_22_and_first_wrong_at_2_23_plus_7_for_8():
+    a = np.arange(1 << 22, dtype=np.int64)
+    for d in FDIV_DIVISORS:  # C / 8 up to 64, and the widths / heights / plane sizes the kernels divide by
+        assert np.array_equal(fdiv_emulated(a, d), a // d), d
+    a = np.arange(1 << 24, dtype=np.int64)  # float32 still holds every such a exactly
+    first = {}
+    for d in (8, 64, 3, 7, 28, 56, 112):
+        wrong = np.nonzero(fdiv_emulated(a, d) != a // d)[0]
+        first[d] = int(wrong[0])
+        assert first[d] >= 1 << 22, (d, first[d])
+    assert first[8] == (1 << 23) + 7 and first[64] == (1 << 23) + 63, first
+    wrong8 = np.nonzero(fdiv_emulated(a, 8) != a // 8)[0]
+    tail = a[(1 << 23):]
+    assert np.array_equal(wrong8, tail[tail % 8 == 7])  # every a = 7 (mod 8) from there on ...
+    assert np.array_equal(fdiv_emulated(wrong8, 8), wrong8 // 8 + 1)  # ... gives q + 1
+    for d in (3, 7, 28, 56, 112):
+        assert 1.4 * (1 << 22) < first[d] < 1.6 * (1 << 22), (d, first[d])
