@@ -848,36 +848,183 @@ __global__ __launch_bounds__(256) void wgrad_scatter_kernel(int C, int Creal, in
 // instead of one or two per convolution (the folds were ~30 launches of 5-12 us each on the critical stream).
 // Record r: dw_r[k][c][tap] += sum_z ws_r[z][k][tap*C + c] (c < Creal), or with a scatter map
 // dw_r[k][map[j]] for source column j = tap*C + c (-1: dropped) -- the stem's 4x4 space-to-depth form
-// gathered back to 7x7x3.  Threads walk the SOURCE order (coalesced slab reads, the bulk of the bytes): a thread
-// owns 4 consecutive source elements (one 16-byte load per split), a block E = 256/SG threads and SG split-groups
-// (thread (sg, e) sums splits sg, sg+SG, ... in batches of 8 loads issued before their adds, the SG partials meet in
-// LDS in order) -- fixed order, deterministic.  The thread's four read-modify-writes of dw issue their loads
-// together: written as four `+=`, each waited for the previous store (possible aliasing), and the 16-byte form ran
-// 245 us per trunk fold (tools/bench_fold.py) against 157 us for the 4-byte form it replaces; now ~146 us.
+// gathered back to 7x7x3.
+//
+// The per-element summation tree is a contract (a different fp32 order grows over the Adam
+// steps into parameter differences far beyond rounding): SG = 8 / 4 / 1 split groups for > 48 / > 12 / fewer slabs;
+// group sg takes slabs sg + SG*i in increasing i, slab i into chain a[i % 4] (each from +0), group partial
+// (a0 + a1) + (a2 + a3); s = 0, s += partial[sg] in order; dw = dw_old + s.  Only additions: any thread mapping that
+// follows the tree gives the same bits.
+//
+// Records without a map are tiled by DESTINATION (fold_tiled): a block owns output channel k and CC channels
+// [c0, c0 + CC) over all RS taps.  Its slab reads are RS segments of CC consecutive floats (whole 128-byte lines),
+// 16 bytes per thread, thread (sg, e) of E = 256/SG summing group sg of tile elements e, e + E, ...; the group
+// partials go to an LDS tile [sg][tap][CC + 4] and the block read-modify-writes the CONTIGUOUS run
+// dw[k][c0 .. c0 + CC)[0 .. RS) in 16-byte vectors (scalar where the run's ends are not 16-byte aligned).  The dw loads
+// are issued first, ahead of the slab loads: one memory round trip per block.  (The source-order form this replaces
+// touched dw in 4-byte pieces RS floats apart, after the sums and the barrier: 163 us per step in the trunk trace.)
+// The stem's map record keeps the source order (fold_source: a thread owns 4 consecutive source elements, block of
+// E threads x SG groups), its map and dw loads hoisted above the slab loop too.
 struct FoldRec {
   const float* ws;
   float* dw;
   const int* map;
   int K, C, Creal, RS, splits, SG, blk0, nblk;
+  int CC, chunks;  // tiled records: channels per block, blocks per output channel
 };
 constexpr int kFoldMaxRecs = 32;
 struct FoldTable {
   int n;
   FoldRec r[kFoldMaxRecs];
 };
+constexpr int kFoldTile = 5120;   // LDS floats: SG * RS * (CC + 4) of a tiled record
+constexpr int kFoldSlots = 5;     // 16-byte dw vectors per thread: RS * CC < kFoldTile
+constexpr int kFoldRunSG = 1016;  // SG > 1: RS * CC at most this -- one dw vector per thread
 
-__global__ __launch_bounds__(256) void wgrad_fold_batch_kernel(FoldTable t) {
-  __shared__ f32x4 part[256];
-  const int v = blockIdx.x;
-  const int ri = table_find(t.n, v, [&](int i) { return t.r[i].blk0; });
-  const FoldRec& R = t.r[ri];
-  const int SG = R.SG, E = 256 / SG, e = threadIdx.x % E, sg = threadIdx.x / E;
+// Group partials of thread (sg, e)'s tile elements base + x*E + e, x < NEB, all at once: NB slab loads per element
+// issued before their adds (clamped addresses, selected adds: no serial tail, no branch between the loads).
+// ONE: n <= NB, a single batch.
+template <int NB, int NEB, bool ONE>
+__device__ __forceinline__ void fold_tile_body(const float* __restrict__ src, long st, int C, int SG, int sg, int e,
+                                               int E, int n, int T4, int cw4, int CCp, float* part, int base) {
+  static_assert(NB % 4 == 0, "chain of slab i is i % 4");
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const float inv_cw4 = 1.f / cw4;
+  int so[NEB], lo[NEB];  // element offsets in the slab row and in the LDS tile
+#pragma unroll
+  for (int x = 0; x < NEB; ++x) {
+    const int q = base + x * E + e, qc = q < T4 ? q : 0;  // (past the tile: loaded, not written)
+    const int tap = fdiv(qc, inv_cw4), c4 = qc - tap * cw4;
+    so[x] = tap * C + c4 * 4;
+    lo[x] = tap * CCp + c4 * 4;
+  }
+  f32x4 a[NEB][4];
+#pragma unroll
+  for (int x = 0; x < NEB; ++x)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[x][c] = zero4;
+  // Every load of a batch is issued, unconditionally, before the first add.  hipcc otherwise moves a load whose add
+  // is conditional into the branch of that add (one load, one wait, ...): the slab count is kept in a vector
+  // register it cannot see through, so the adds are selects, and each loaded value passes through an empty asm
+  // statement in front of its add, which keeps the load out of any branch.
+  int nv = n;
+  asm volatile("" : "+v"(nv));
+  auto batch = [&](int i0) {
+    f32x4 w[NEB][NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int i = i0 + b < nv ? i0 + b : nv - 1;
+      const float* slab = src + (long)(__mul24(SG, i) + sg) * st;  // slab sg + SG*i
+#pragma unroll
+      for (int x = 0; x < NEB; ++x) w[x][b] = *reinterpret_cast<const f32x4*>(slab + so[x]);
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int x = 0; x < NEB; ++x) {
+        asm volatile("" : "+v"(w[x][b]));
+        if (i0 + b < nv) a[x][b & 3] += w[x][b];
+      }
+  };
+  // the first batch outside the loop: straight-line code behind the dw loads (hipcc drains the loads in flight, the
+  // dw loads too, in front of a loop that loads)
+  if (n > 0) batch(0);
+  if (!ONE)
+    for (int i0 = NB; i0 < n; i0 += NB) batch(i0);
+#pragma unroll
+  for (int x = 0; x < NEB; ++x)
+    if (base + x * E + e < T4) *reinterpret_cast<f32x4*>(part + lo[x]) = (a[x][0] + a[x][1]) + (a[x][2] + a[x][3]);
+}
+
+// The thread's ceil(T4 / E) <= kFoldSlots tile elements in groups of 4, 2 and 1 (at most 16 loads in flight per
+// thread); no loop, see above
+template <int NB, bool ONE>
+__device__ __forceinline__ void fold_tile_sum(const float* __restrict__ src, long st, int C, int SG, int sg, int e,
+                                              int E, int n, int T4, int cw4, int CCp, float* part) {
+  constexpr int G = NB * 4 <= 16 ? 4 : (NB * 2 <= 16 ? 2 : 1);  // elements per group
+  int base = 0, ne = (T4 + E - 1) / E;                            // block-uniform
+#pragma unroll
+  for (int g = 0; g < kFoldSlots / G; ++g)
+    if (ne >= G) {
+      fold_tile_body<NB, G, ONE>(src, st, C, SG, sg, e, E, n, T4, cw4, CCp, part, base);
+      ne -= G, base += G * E;
+    }
+  if constexpr (G == 4)
+    if (ne >= 2) {
+      fold_tile_body<NB, 2, ONE>(src, st, C, SG, sg, e, E, n, T4, cw4, CCp, part, base);
+      ne -= 2, base += 2 * E;
+    }
+  if constexpr (G >= 2)
+    if (ne >= 1) fold_tile_body<NB, 1, ONE>(src, st, C, SG, sg, e, E, n, T4, cw4, CCp, part, base);
+}
+
+template <int NSLOT>
+__device__ __forceinline__ void fold_tiled(const FoldRec& R, int lb, float* lds) {
+  const int SG = R.SG, E = 256 / SG, tid = threadIdx.x, e = tid & (E - 1), sg = tid / E;
+  const int RS = R.RS, k = lb / R.chunks, c0 = (lb - k * R.chunks) * R.CC;
+  const int cw = min(R.CC, ((R.Creal + 3) & ~3) - c0), cw4 = cw >> 2, CCp = R.CC + 4;  // channels read
+  const int L = min(cw, R.Creal - c0) * RS;  // floats of the dw run (channels c >= Creal are dropped)
+  float* __restrict__ dst = R.dw + ((long)k * R.Creal + c0) * RS;
+  // the run = `head` floats up to the first 16-byte boundary, nb whole 16-byte vectors (thread tid: vectors tid,
+  // tid + 256, ...), `tail` floats; the head and tail floats go one each to threads 0-2 and 3-5
+  const int head = min((4 - (int)(((uintptr_t)dst >> 2) & 3)) & 3, L), nb = (L - head) >> 2, tail0 = head + 4 * nb;
+  const int ei = tid < 3 ? tid : tail0 + tid - 3;
+  const bool edge = tid < 3 ? tid < head : (tid < 6 && ei < L);
+  const long row = (long)RS * R.C, total = (long)R.K * row;
+  const float* src = R.ws + (long)k * row + c0;
+  // the dw loads first (their addresses need nothing but the block's place), branch-free: a thread without a j-th
+  // vector re-reads the run's last one (a run shorter than a vector: 16 bytes of the slab, unused)
+  const float* dwv = nb > 0 ? dst + head : src;
+  f32x4 d[NSLOT];
+#pragma unroll
+  for (int j = 0; j < NSLOT; ++j) d[j] = *reinterpret_cast<const f32x4*>(dwv + 4 * min(tid + 256 * j, max(nb - 1, 0)));
+  const float de = dst[edge ? ei : 0];
+  const int splits = R.splits, n = splits > sg ? (splits - sg + SG - 1) / SG : 0, T4 = RS * cw4;
+  float* part = lds + sg * RS * CCp;
+  // few slabs (layer3 / layer4: SG = 1, at most 12): every slab of 4 / 2 / 1 elements in flight at once; else batches
+  // of 8 slabs of 2 elements
+  if (NSLOT == 1) fold_tile_sum<8, false>(src, total, R.C, SG, sg, e, E, n, T4, cw4, CCp, part);
+  else if (splits <= 4) fold_tile_sum<4, true>(src, total, R.C, 1, 0, e, E, n, T4, cw4, CCp, part);
+  else if (splits <= 8) fold_tile_sum<8, true>(src, total, R.C, 1, 0, e, E, n, T4, cw4, CCp, part);
+  else fold_tile_sum<12, true>(src, total, R.C, 1, 0, e, E, n, T4, cw4, CCp, part);
+  __syncthreads();
+  const float inv_RS = 1.f / RS;
+  auto sum_at = [&](int i) {  // s of run element i = cl*RS + tap: the group partials in order
+    const int cl = fdiv(i, inv_RS), tap = i - cl * RS;
+    float s = 0.f;
+    for (int q = 0; q < SG; ++q) s += lds[(q * RS + tap) * CCp + cl];
+    return s;
+  };
+#pragma unroll
+  for (int j = 0; j < NSLOT; ++j)
+    if (tid + 256 * j < nb) {
+      const int i = head + 4 * (tid + 256 * j);
+      f32x4 r;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) r[x] = d[j][x] + sum_at(i + x);
+      *reinterpret_cast<f32x4*>(dst + i) = r;
+    }
+  if (edge) dst[ei] = de + sum_at(ei);
+}
+
+__device__ __forceinline__ void fold_source(const FoldRec& R, int lb, f32x4* part) {
+  const int SG = R.SG, E = 256 / SG, e = threadIdx.x & (E - 1), sg = threadIdx.x / E;
   const long row = (long)R.RS * R.C, total = (long)R.K * row;
-  const int lb = v - R.blk0;
   const long idx = ((long)lb * E + e) * 4;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 a0 = zero4, a1 = zero4, a2 = zero4, a3 = zero4;
   const int splits = R.splits;
+  const bool writer = sg == 0 && idx < total;
+  const int k = (int)(idx / row), j0 = (int)(idx - (long)k * row);
+  float* __restrict__ dwk = R.dw + (long)k * R.Creal;
+  int o[4] = {-1, -1, -1, -1};
+  float d[4] = {0.f, 0.f, 0.f, 0.f};
+  if (writer) {  // map and dw loads ahead of the slab loads
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) o[c4] = R.map[j0 + c4];
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) d[c4] = dwk[o[c4] >= 0 ? o[c4] : 0];  // the 4 read-modify-writes' loads together
+  }
   if (idx < total) {
     const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(R.ws + idx);
     const long st = total / 4;
@@ -903,29 +1050,22 @@ __global__ __launch_bounds__(256) void wgrad_fold_batch_kernel(FoldTable t) {
   }
   part[threadIdx.x] = (a0 + a1) + (a2 + a3);
   __syncthreads();
-  if (sg != 0 || idx >= total) return;
+  if (!writer) return;
   f32x4 s4 = zero4;
   for (int q = 0; q < SG; ++q) s4 += part[q * E + e];
-  const long per_k = R.map ? (long)R.Creal : (long)R.Creal * R.RS;
-  const int k = (int)(idx / row), j0 = (int)(idx - (long)k * row);
-  int o[4];
-  float d[4];
-  float* __restrict__ dwk = R.dw + (long)k * per_k;
-#pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4) {
-    const int j = j0 + c4;
-    if (R.map) {
-      o[c4] = R.map[j];
-    } else {
-      const int tap = j / R.C, c = j - tap * R.C;
-      o[c4] = c < R.Creal ? c * R.RS + tap : -1;
-    }
-  }
-#pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4) d[c4] = dwk[o[c4] >= 0 ? o[c4] : 0];  // the 4 read-modify-writes' loads together
 #pragma unroll
   for (int c4 = 0; c4 < 4; ++c4)
     if (o[c4] >= 0) dwk[o[c4]] = d[c4] + s4[c4];
+}
+
+__global__ __launch_bounds__(256) void wgrad_fold_batch_kernel(FoldTable t) {
+  __shared__ __attribute__((aligned(16))) float lds[kFoldTile];
+  const int v = blockIdx.x;
+  const int ri = table_find(t.n, v, [&](int i) { return t.r[i].blk0; });
+  const FoldRec& R = t.r[ri];
+  if (R.map) fold_source(R, v - R.blk0, reinterpret_cast<f32x4*>(lds));
+  else if (R.SG > 1) fold_tiled<1>(R, v - R.blk0, lds);
+  else fold_tiled<kFoldSlots>(R, v - R.blk0, lds);
 }
 
 }  // namespace
@@ -1047,7 +1187,31 @@ MER_API int mer_wgrad_fold_batch(int n, const long long* rows, void* stream) {
     r.SG = r.splits > 48 ? fold_sg_max() : (r.splits > 12 ? 4 : 1);
     const long total = (long)r.K * r.RS * r.C;
     r.blk0 = blk;
-    r.nblk = (int)((total + 4 * (256 / r.SG) - 1) / (4 * (256 / r.SG)));
+    if (r.map) {  // source order: E = 256/SG threads of 4 floats per block
+      r.nblk = (int)((total + 4 * (256 / r.SG) - 1) / (4 * (256 / r.SG)));
+    } else {
+      // a 1x1 record's slab and dw are the same flat [K*C] order: fold it as rows of 1024 channels (a 64-channel row
+      // alone would leave most of a block idle)
+      if (r.RS == 1 && r.Creal == r.C && r.C < 1024 && total % 1024 == 0) {
+        r.K = (int)(total / 1024);
+        r.C = r.Creal = 1024;
+      }
+      // channels per block: the whole row for the few-slab records (SG = 1: several 16-byte elements and all their
+      // slabs in flight per thread); for the many-slab ones the smallest multiple of 32 (whole 128-byte lines) that
+      // gives each thread of a split group an element -- short rows cut into many blocks
+      const int E = 256 / r.SG, cr4 = (r.Creal + 3) & ~3;
+      int cap = (kFoldTile / (r.SG * r.RS) - 4) & ~3;
+      if (r.SG > 1) cap = std::min(cap, (kFoldRunSG / r.RS) & ~3);
+      if (cap < 4) return (int)hipErrorInvalidValue;
+      int cc = cr4;
+      if (r.SG > 1)
+        for (cc = 32; r.RS * cc / 4 < E && cc < cr4;) cc *= 2;
+      cc = std::min(std::min(cc, cr4), cap);
+      if (cc > 32) cc &= ~31;
+      r.CC = cc;
+      r.chunks = (cr4 + cc - 1) / cc;
+      r.nblk = r.K * r.chunks;
+    }
     blk += r.nblk;
   }
   hipLaunchKernelGGL(wgrad_fold_batch_kernel, dim3(blk), dim3(256), 0, (hipStream_t)stream, t);
