@@ -768,6 +768,58 @@ int mer_adaptive_avgpool_seq(int B, int C, int H, int W, int bins, const float* 
 /* The same from the frame trunk's activation layout: x bf16 NHWC [B][H][W][C] -> y fp32 [B][bins][C]. */
 int mer_adaptive_avgpool_seq_nhwc(int B, int H, int W, int C, int bins, const void* x, float* y, void* stream);
 
+/* ---- AudioCNN in training mode (csrc/audionet_train.hip), fp32 NCHW.  Every entry point checks its arguments and
+ * returns hipErrorInvalidValue before any launch; no atomics, every reduction in an order fixed by the shape. ---- */
+
+/* z = conv3x3(x, pad 1) + bias (bias may be NULL), no BatchNorm: x [B][Cin][H][W] -> z [B][Cout][H][W].
+ * transposed = 0: the forward, w [Cout][Cin][3][3], (Cin, Cout) = (1, 16), (16, 32), (32, 64).
+ * transposed = 1: the data gradient of a forward layer, x = dz, w the FORWARD weight [Cin][Cout][3][3] (used flipped),
+ * (Cin, Cout) = (64, 32), (32, 16).  wpack: 9 * Cin * Cout floats of scratch unless Cin = 1. */
+int mer_audiocnn_train_conv(int B, int H, int W, int Cin, int Cout, int transposed, const float* x, const float* w,
+                            const float* bias, float* wpack, float* z, void* stream);
+
+/* Batch statistics of z [B][C][HW] per channel (B * HW >= 2): per-plane (mean, M2) merged by Chan's formula in image
+ * order.  ss [C][4] = scale, shift, mean, invstd (scale = gamma * invstd, shift = beta - mean * scale, biased
+ * variance); running_mean / running_var (may be NULL) move by momentum towards the mean / the unbiased variance and
+ * num_batches_tracked (int64 [1], may be NULL) grows by one.  A plane is reduced in MER_BN_PLANE_CHUNKS(HW) chunks;
+ * part: 2 * B * C * MER_BN_PLANE_CHUNKS(HW) floats of scratch. */
+#define MER_BN_PLANE_CHUNK 4096
+#define MER_BN_PLANE_CHUNKS(HW) (((HW) + MER_BN_PLANE_CHUNK - 1) / MER_BN_PLANE_CHUNK)
+int mer_bn_train_stats(int B, int C, int HW, const float* z, const float* gamma, const float* beta, float eps,
+                       float momentum, float* part, float* ss, float* running_mean, float* running_var,
+                       long* num_batches_tracked, void* stream);
+
+/* y = relu(z * scale + shift) [B][C][H][W], or with pool its MaxPool2d(2) [B][C][H/2][W/2]; ss of mer_bn_train_stats. */
+int mer_bn_relu_pool_fwd(int B, int C, int H, int W, int pool, const float* z, const float* ss, float* y, void* stream);
+
+/* Backward of mer_bn_relu_pool_fwd and of the batch-statistics BatchNorm in front of it.  g: gradient of y.  The
+ * arg-max (first maximum in window order) and the ReLU mask bn(z) > 0 are recomputed from z and ss.
+ * dgamma / dbeta / dbias [C] (each may be NULL) are ACCUMULATED; dbias is the channel sum of dz.
+ * Either dz [B][C][H][W] is written (the gradient of z, over the whole map), or -- one input channel -- x [B][1][H][W]
+ * and dw1 [C][3][3] are given and the conv's weight gradient is accumulated into dw1 without storing dz.
+ * part: MER_BN_RELU_POOL_BWD_WS(B, C, H * W) floats of scratch. */
+#define MER_BN_RELU_POOL_BWD_WS(B, C, HW) ((12L * (C) + 1) * (B) * MER_BN_PLANE_CHUNKS(HW) + 2L * (C) + 1)
+int mer_bn_relu_pool_bwd(int B, int C, int H, int W, int pool, const float* z, const float* ss, const float* g,
+                         float* part, float* dgamma, float* dbeta, float* dbias, float* dz, const float* x, float* dw1,
+                         void* stream);
+
+/* dw [Cout][Cin][3][3] += the weight gradient of the 3x3 / pad 1 conv from its input x [B][Cin][H][W] and
+ * dz [B][Cout][H][W]; (Cin, Cout) = (16, 32), (32, 64).  part: rows * 9 * Cin * Cout floats of scratch with
+ * rows = min(B * ceil(H / 4) * ceil(W / 16), MER_AUDIOCNN_WGRAD_WGS) * (64 / Cout). */
+#define MER_AUDIOCNN_WGRAD_WGS 256
+int mer_audiocnn_wgrad(int B, int H, int W, int Cin, int Cout, const float* x, const float* dz, float* part, float* dw,
+                       void* stream);
+
+/* Backward of mer_adaptive_avgpool_seq: g [B][bins][C] -> dx [B][C][H][W] (written, not accumulated). */
+int mer_adaptive_avgpool_seq_bwd(int B, int C, int H, int W, int bins, const float* g, float* dx, void* stream);
+
+/* SpecAugment's masked copy: y = x [planes][n_mels][T] with n_freq bands of rows and n_time bands of columns zeroed
+ * (the same for every plane).  freq_bands / time_bands: HOST arrays of (start, length) pairs, at most
+ * MER_SPEC_AUGMENT_MAX_BANDS each, passed on in the kernel arguments; y must not be x. */
+#define MER_SPEC_AUGMENT_MAX_BANDS 8
+int mer_spec_augment_mask(long planes, int n_mels, int T, const float* x, float* y, int n_freq, const int* freq_bands,
+                          int n_time, const int* time_bands, void* stream);
+
 /* ============================ timeline over a recording (timeline.py) ============================
  * Overlapping windows of one long recording whose frames are encoded once.  idx arrays are DEVICE int32; the Python
  * wrappers validate them on the host, and the kernels clamp every index into [0, n_src) so that no launch reads

@@ -891,6 +891,152 @@ def adaptive_avgpool_seq_nhwc(x, bins):
     return y
 
 
+# ---- AudioCNN in training mode (csrc/audionet_train.hip) ----
+AUDIOCNN_WGRAD_WGS = 256  # MER_AUDIOCNN_WGRAD_WGS
+BN_PLANE_CHUNK = 4096  # MER_BN_PLANE_CHUNK
+SPEC_AUGMENT_MAX_BANDS = 8  # MER_SPEC_AUGMENT_MAX_BANDS
+_AUDIOCNN_LAYERS = ((1, 16), (16, 32), (32, 64))
+
+
+def _check_f32c(name, *ts):
+    _check_dev(*ts)
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name}: contiguous fp32 tensors expected")
+
+
+def audiocnn_train_conv(x, weight, bias):
+    """z = conv3x3(x, padding 1) + bias of one AudioCNN layer, before BatchNorm: fp32 [B, Cin, H, W] -> [B, Cout, H, W]."""
+    _check_f32c("audiocnn_train_conv", x, weight, bias)
+    B, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, Cin, 3, 3) or (Cin, Cout) not in _AUDIOCNN_LAYERS \
+            or (bias is not None and bias.numel() != Cout):
+        raise ValueError(f"audiocnn_train_conv: unsupported layer x{tuple(x.shape)} w{tuple(weight.shape)}")
+    z = torch.empty(B, Cout, H, W, device=x.device, dtype=torch.float32)
+    wpack = _workspace(9 * Cin * Cout, x.device) if Cin > 1 else None
+    LIB("mer_audiocnn_train_conv", B, H, W, Cin, Cout, 0, x.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(wpack),
+        z.data_ptr(), stream_ptr())
+    return z
+
+
+def audiocnn_dgrad(dz, weight):
+    """Data gradient of an AudioCNN conv: dz [B, Cout, H, W], the forward weight [Cout, Cin, 3, 3] -> dx [B, Cin, H, W]."""
+    _check_f32c("audiocnn_dgrad", dz, weight)
+    B, Cout, H, W = dz.shape
+    Cin = weight.shape[1]
+    if tuple(weight.shape) != (Cout, Cin, 3, 3) or (Cin, Cout) not in _AUDIOCNN_LAYERS[1:]:
+        raise ValueError(f"audiocnn_dgrad: unsupported layer dz{tuple(dz.shape)} w{tuple(weight.shape)}")
+    dx = torch.empty(B, Cin, H, W, device=dz.device, dtype=torch.float32)
+    wpack = _workspace(9 * Cin * Cout, dz.device)
+    LIB("mer_audiocnn_train_conv", B, H, W, Cout, Cin, 1, dz.data_ptr(), weight.data_ptr(), 0, wpack.data_ptr(),
+        dx.data_ptr(), stream_ptr())
+    return dx
+
+
+def bn_train_stats(z, bn):
+    """Batch statistics of z [B, C, H, W] for ``bn`` in training mode: returns ss [C, 4] = scale, shift, mean, invstd and
+    updates the module's running statistics and ``num_batches_tracked`` (when it tracks them)."""
+    _check_f32c("bn_train_stats", z, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    B, C, H, W = z.shape
+    if bn.weight is None or bn.weight.numel() != C:
+        raise ValueError("bn_train_stats needs an affine BatchNorm2d of the map's channel count")
+    if bn.momentum is None:
+        raise ValueError("bn_train_stats: momentum=None (cumulative average) is not built")
+    if B * H * W < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+    nbt = bn.num_batches_tracked if bn.running_mean is not None else None
+    if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
+        raise ValueError("bn_train_stats: num_batches_tracked must be a device int64 tensor")
+    ss = torch.empty(C, 4, device=z.device, dtype=torch.float32)
+    part = _workspace(2 * B * C * -(-H * W // BN_PLANE_CHUNK), z.device)
+    LIB("mer_bn_train_stats", B, C, H * W, z.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
+        float(bn.momentum), part.data_ptr(), ss.data_ptr(), _ptr(bn.running_mean), _ptr(bn.running_var), _ptr(nbt),
+        stream_ptr())
+    return ss
+
+
+def bn_relu_pool_fwd(z, ss, pool):
+    """relu(z * scale + shift), then MaxPool2d(2) when ``pool``."""
+    _check_f32c("bn_relu_pool_fwd", z, ss)
+    B, C, H, W = z.shape
+    if tuple(ss.shape) != (C, 4) or (pool and (H < 2 or W < 2)):
+        raise ValueError(f"bn_relu_pool_fwd: bad operands z{tuple(z.shape)} ss{tuple(ss.shape)} pool={pool}")
+    y = torch.empty(B, C, H // 2 if pool else H, W // 2 if pool else W, device=z.device, dtype=torch.float32)
+    LIB("mer_bn_relu_pool_fwd", B, C, H, W, int(bool(pool)), z.data_ptr(), ss.data_ptr(), y.data_ptr(), stream_ptr())
+    return y
+
+
+def bn_relu_pool_bwd(z, ss, g, pool, dgamma=None, dbeta=None, dbias=None, x=None, dw1=None):
+    """Backward of ``bn_relu_pool_fwd`` and the batch-statistics BatchNorm: accumulates dgamma / dbeta / dbias [C]
+    (each optional) and returns dz [B, C, H, W] -- or, with the one-channel conv input ``x`` and ``dw1`` [C, 1, 3, 3],
+    accumulates that conv's weight gradient and returns None (dz is never stored)."""
+    _check_f32c("bn_relu_pool_bwd", z, ss, g, dgamma, dbeta, dbias, x, dw1)
+    B, C, H, W = z.shape
+    gs = (B, C, H // 2, W // 2) if pool else (B, C, H, W)
+    if tuple(ss.shape) != (C, 4) or tuple(g.shape) != gs or any(t is not None and t.numel() != C
+                                                                for t in (dgamma, dbeta, dbias)):
+        raise ValueError(f"bn_relu_pool_bwd: bad operands z{tuple(z.shape)} g{tuple(g.shape)} pool={pool}")
+    if (x is None) != (dw1 is None) or (x is not None and (tuple(x.shape) != (B, 1, H, W) or dw1.numel() != 9 * C)):
+        raise ValueError("bn_relu_pool_bwd: x [B, 1, H, W] and dw1 [C, 1, 3, 3] go together")
+    dz = torch.empty_like(z) if x is None else None
+    part = _workspace((12 * C + 1) * B * -(-H * W // BN_PLANE_CHUNK) + 2 * C + 1, z.device)  # MER_BN_RELU_POOL_BWD_WS
+    LIB("mer_bn_relu_pool_bwd", B, C, H, W, int(bool(pool)), z.data_ptr(), ss.data_ptr(), g.data_ptr(), part.data_ptr(),
+        _ptr(dgamma), _ptr(dbeta), _ptr(dbias), _ptr(dz), _ptr(x), _ptr(dw1), stream_ptr())
+    return dz
+
+
+def audiocnn_wgrad_rows(B, H, W, Cout):
+    """Partial rows ``mer_audiocnn_wgrad`` writes: a function of the shape alone."""
+    return min(B * ((H + 3) // 4) * ((W + 15) // 16), AUDIOCNN_WGRAD_WGS) * (64 // Cout)
+
+
+def audiocnn_wgrad(x, dz, dw):
+    """dw [Cout, Cin, 3, 3] += weight gradient of the 3x3 conv from its input x and dz (layers 2 and 3)."""
+    _check_f32c("audiocnn_wgrad", x, dz, dw)
+    B, Cin, H, W = x.shape
+    Cout = dz.shape[1]
+    if tuple(dz.shape) != (B, Cout, H, W) or tuple(dw.shape) != (Cout, Cin, 3, 3) \
+            or (Cin, Cout) not in _AUDIOCNN_LAYERS[1:]:
+        raise ValueError(f"audiocnn_wgrad: unsupported layer x{tuple(x.shape)} dz{tuple(dz.shape)} dw{tuple(dw.shape)}")
+    part = _workspace(audiocnn_wgrad_rows(B, H, W, Cout) * 9 * Cin * Cout, x.device)
+    LIB("mer_audiocnn_wgrad", B, H, W, Cin, Cout, x.data_ptr(), dz.data_ptr(), part.data_ptr(), dw.data_ptr(),
+        stream_ptr())
+
+
+def adaptive_avgpool_seq_bwd(g, H, W):
+    """Backward of ``adaptive_avgpool_seq``: g fp32 [B, bins, C] -> dx [B, C, H, W]."""
+    _check_f32c("adaptive_avgpool_seq_bwd", g)
+    if g.dim() != 3 or H < 1 or W < 1:
+        raise ValueError("adaptive_avgpool_seq_bwd takes contiguous fp32 [B, bins, C]")
+    B, bins, C = g.shape
+    dx = torch.empty(B, C, int(H), int(W), device=g.device, dtype=torch.float32)
+    LIB("mer_adaptive_avgpool_seq_bwd", B, C, int(H), int(W), bins, g.data_ptr(), dx.data_ptr(), stream_ptr())
+    return dx
+
+
+def spec_augment_mask(x, freq_bands, time_bands):
+    """A copy of x [..., n_mels, T] with the (start, length) bands of rows / columns zeroed; the bands are host
+    values that travel in the kernel arguments (no copy to the device, no synchronisation)."""
+    import ctypes
+
+    _check_f32c("spec_augment_mask", x)
+    if x.dim() < 2:
+        raise ValueError("spec_augment_mask takes [..., n_mels, T]")
+    n_mels, T = x.shape[-2:]
+    arrs = []
+    for bands, size in ((freq_bands, n_mels), (time_bands, T)):
+        if len(bands) > SPEC_AUGMENT_MAX_BANDS:
+            raise ValueError(f"spec_augment_mask: at most {SPEC_AUGMENT_MAX_BANDS} bands per axis")
+        if any(s < 0 or n < 0 or s + n > size for s, n in bands):
+            raise ValueError(f"spec_augment_mask: band outside 0..{size}: {list(bands)}")
+        arrs.append((ctypes.c_int * (2 * max(1, len(bands))))(*[int(v) for b in bands for v in b]))
+    y = torch.empty_like(x)
+    LIB("mer_spec_augment_mask", x.numel() // (n_mels * T), n_mels, T, x.data_ptr(), y.data_ptr(), len(freq_bands),
+        ctypes.cast(arrs[0], ctypes.c_void_p), len(time_bands), ctypes.cast(arrs[1], ctypes.c_void_p), stream_ptr())
+    return y
+
+
 def softmax_avg_fwd(za, zv, out, pa, pv):
     B, C = za.shape
     LIB("mer_softmax_avg_fwd", B, C, za.data_ptr(), zv.data_ptr(), out.data_ptr(), pa.data_ptr(), pv.data_ptr(),

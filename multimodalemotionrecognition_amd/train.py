@@ -46,7 +46,8 @@ def build_model(num_classes: int, fusion: str, pretrained_video: bool = True, xa
     Reference quirk kept on purpose: the reference never forwards the ``xattn_use_emotion_prior*``
     flags to ``FusionModel`` (train.py:454-469, eval.py:182-197), so its checkpoints have no prior
     weights; pass ``forward_emotion_prior_flags=True`` to actually enable the prior-bias path.
-    ``use_wavlm=False`` builds the mel ``AudioNet`` (audio.py), which runs in eval mode only.
+    ``use_wavlm=False`` builds the mel ``AudioNet`` (audio.py), which trains over ``AudioCNN``
+    (``use_resnet_audio=False``); over ``AudioResNet18`` it runs in eval mode only.
     """
     tp = dict(temporal_pooling=temporal_pooling, temporal_num_heads=temporal_num_heads,
               temporal_num_layers=temporal_num_layers, temporal_dropout=temporal_dropout)
