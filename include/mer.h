@@ -876,6 +876,35 @@ int mer_ring_windows(int B, long target, const float* rings, int n_slots, long c
  * and both bases are 16-byte aligned, scalar otherwise (as mer_rows_gather). */
 int mer_rows_scatter(int n_dst, int n_rows, int D, const float* src, const int* idx, float* dst, void* stream);
 
+/* ============================ audio clip assembly (clips.assemble_waveforms) ============================
+ * What load_audio_wav does after decoding, for a batch: resample + pad / crop, then the train-split noise mix. */
+
+/* out fp32 [B][target]: clip b = packed[offsets[b] .. offsets[b] + lengths[b]) (DEVICE int64 [B] each, any alignment)
+ * resampled by up / down with mer_resample_stream's filter, table and per-output arithmetic (the same device
+ * function: a clip and a stream fed the clip then zeros give the same bits).  A clip is 0 before its first and after
+ * its last sample -- its neighbours in the packed buffer are never read; clip b has nout_b = ceil(len_b * up / down)
+ * outputs, outputs [nout_b, target) are 0 (the pad), outputs past target are not computed (the crop); len_b == 0 gives a
+ * zero row; up == down == 1 is a copy / crop (table unused).  Output target - 1 reads no input past
+ * ((target - 1) * down + half) / up, so the caller need not send more.  kmax = 2 * half / up + 1; rates whose
+ * per-block input span 255 * down / up + 1 + kmax exceeds 12,288 floats are refused as in mer_resample_stream.
+ * No atomics: the result depends on neither B nor where a clip sits in packed.  B <= 65535. */
+int mer_resample_clips(int B, long target, int up, int down, int kmax, const float* table, const float* packed,
+                       const long* offsets, const long* lengths, float* out, void* stream);
+
+/* The noise mix of ravdess.py:539-576 (host/mer_io.cpp mer_mix_noise) on wav fp32 [B][target] -> out (a distinct
+ * buffer).  Per-clip DEVICE descriptors: mode int32 [B] (0 leave alone, 1 noise track, 2 Gaussian), start int64 [B]
+ * (>= 0), snr_db fp32 [B], seed uint64 [B].  Three launches: (A) parts fp64 [B][ceil(target / 256)][2] = per-block
+ * (sum wav^2, sum v^2), v = noise[(start + i) % n_noise]; (fold) ps, pn = the partials summed in block order / target,
+ * want = ps / max(10^(snr_db / 10), 1e-8); (B) the output:
+ *   mode 1: scale = pn > 1e-8 ? (float)sqrt(want / pn) : 1;  out = clamp(fl(wav + fl(v * scale)), -1, 1)
+ *   mode 2: scale = (float)sqrt(want) (the sigma);  out = clamp(fl(wav + fl(z * scale)), -1, 1) with
+ *           z = ztable[hash(seed, i) >> 16], the augmentation's 65,536-entry inverse normal CDF
+ *   mode 0: scale = 0; out = wav bit for bit, NOT clamped (the reference clamps augmented clips only).
+ * noise fp32 [n_noise] (may be NULL with n_noise == 0 when no clip has mode 1); scale fp32 [B] is an output. */
+int mer_mix_noise_clips(int B, long target, const float* wav, const int* mode, const long* start, const float* snr_db,
+                        const unsigned long long* seed, const float* noise, long n_noise, const float* ztable,
+                        double* parts, float* scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,8 +20,13 @@ decoded uint8 frames / raw waveforms cross PCIe and the batch is assembled in HB
 * ``ResampleStream`` -- a live stream resampled once, chunk by chunk, into a device ring (``streaming.py``; the
   windows come out of the rings through ``kernels.ring_windows``).
 
-Decoding (cv2.VideoCapture / librosa), face detection / crop and the audio augmentation stay on the host
-(DESIGN.md section 4c).  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``, ``csrc/timeline.hip``, ``csrc/stream.hip``;
+* ``resample_clips`` / ``mix_noise_clips`` / ``assemble_waveforms`` -- ``load_audio_wav`` after the decode for a whole
+  batch: ragged clips at their native rates resampled (the stream's arithmetic, bit for bit), padded / cropped and
+  mixed with the bar-noise track at the drawn SNR (``draw_audio_augment``: the host's draws in the host's order).
+
+Decoding (cv2.VideoCapture / librosa) and face detection / crop stay on the host, and so does the audio path of the
+default ``ClipLoader``.  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``, ``csrc/timeline.hip``,
+``csrc/stream.hip``, ``csrc/audio_clips.hip``;
 CPU restatements:
 ``oracle/clips_ref.py``, ``tests/mel_ref.py``.
 """
@@ -340,6 +345,237 @@ class ResampleStream:
               self.counts.data_ptr(), K.stream_ptr())
         self._cur = new
         return self.count.advance(n)
+
+
+def resample_plan(sr_in: int, sr_out: int):
+    """``(up, down, kmax)`` of a whole-clip resample, refused on the host when a workgroup's input span would not fit
+    the resampler's LDS limit (``kmax`` is 0 for equal rates: a copy)."""
+    up, down = resample_ratio(sr_in, sr_out)
+    if up == 1 and down == 1:
+        return up, down, 0
+    kmax = 2 * 10 * max(up, down) // up + 1
+    if 255 * down // up + 1 + kmax > RESAMPLE_MAX_SPAN:
+        raise ValueError(f"sample rate {sr_in}: the resampler stages at most {RESAMPLE_MAX_SPAN} inputs per block")
+    return up, down, kmax
+
+
+def _polyphase(dev, up: int, down: int) -> torch.Tensor:
+    key = (dev, up, down)
+    t = _POLYPHASE.get(key)
+    if t is None:
+        t = _POLYPHASE[key] = polyphase_table(up, down).to(dev)
+    return t
+
+
+def resample_outputs(n_in: int, up: int, down: int) -> int:
+    """``ceil(n_in * up / down)``: the outputs of a whole clip of ``n_in`` samples (scipy ``resample_poly``)."""
+    return -(-int(n_in) * int(up) // int(down))
+
+
+def resample_needed_inputs(target: int, up: int, down: int) -> int:
+    """How many leading input samples the first ``target`` outputs of a resampled clip read: output ``target - 1``
+    has newest input ``floor(((target - 1) * down + half) / up)``, ``half = 10 * max(up, down)``, so one more than
+    that.  A clip sliced to this length gives the same first ``target`` outputs as the whole clip."""
+    target, up, down = int(target), int(up), int(down)
+    if target <= 0:
+        return 0
+    if up == 1 and down == 1:
+        return target
+    return ((target - 1) * down + 10 * max(up, down)) // up + 1
+
+
+def _pack_clips(wavs, dev):
+    """Ragged 1-D fp32 clips -> (packed device buffer, host offsets, host lengths)."""
+    flat = [w.reshape(-1) for w in wavs]
+    for w in flat:
+        if w.dtype != torch.float32:
+            raise ValueError("waveforms must be fp32")
+    lengths = [int(w.numel()) for w in flat]
+    offsets = [0]
+    for n in lengths[:-1]:
+        offsets.append(offsets[-1] + n)
+    if not sum(lengths):
+        packed = torch.zeros(1, device=dev)
+    elif all(not w.is_cuda for w in flat):  # gathered straight into ONE pinned host buffer (one pass), one H2D copy
+        stage = torch.empty(sum(lengths), dtype=torch.float32, pin_memory=True)
+        torch.cat(flat, out=stage)
+        packed = stage.to(dev, non_blocking=True)  # the caching host allocator keeps the block until the copy ran
+    else:
+        packed = torch.cat([w.to(dev) if w.is_cuda else _h2d(w.contiguous(), dev) for w in flat])
+    return packed, offsets, lengths
+
+
+def resample_clips(wavs, sample_rate_in: int, sample_rate_out: int = 16000, target: int = None, device=None,
+                   out: torch.Tensor = None) -> torch.Tensor:
+    """Whole clips resampled on the GPU, ``sample_rate_in`` -> ``sample_rate_out``, zero-padded at the end or cropped
+    to ``target`` outputs each: ``[B, target]`` fp32 (mer_resample_clips, one launch for the batch).
+
+    ``wavs``: a ragged list of 1-D fp32 clips, or one tensor (1-D: one clip; 2-D: one clip per row), host or device,
+    all at ``sample_rate_in``.  The filter is scipy ``resample_poly``'s (``polyphase_table``), a clip is zero outside
+    its own samples, and every output has the bits ``ResampleStream`` gives for the same clip.  ``target=None`` keeps
+    each clip's own ``ceil(len * up / down)`` outputs, so it takes one clip or clips of equal output count.  Outputs
+    past ``target`` are never computed; ``resample_needed_inputs`` says how much of a clip they read.  ``out``: a
+    contiguous fp32 ``[B, target]`` device tensor to write into.  Rates are refused (``ValueError``) before any
+    device work when not positive or when a block's input span exceeds the resampler's LDS limit."""
+    up, down, kmax = resample_plan(sample_rate_in, sample_rate_out)
+    if isinstance(wavs, torch.Tensor):
+        if wavs.dim() not in (1, 2):
+            raise ValueError("resample_clips takes a list of 1-D clips or one 1-D / 2-D tensor")
+        wavs = [wavs] if wavs.dim() == 1 else list(wavs.unbind(0))
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError("empty waveform batch")
+    dev = torch.device(device) if device is not None else next((w.device for w in wavs if w.is_cuda), None)
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("resample_clips runs on the MI355X kernels; pass device='cuda'")
+    if target is None:
+        nouts = {resample_outputs(w.numel(), up, down) for w in wavs}
+        if len(nouts) != 1:
+            raise ValueError("target=None takes one clip or clips of equal output count; pass target")
+        target = nouts.pop()
+    packed, offsets, lengths = _pack_clips(wavs, dev)
+    return resample_packed(packed, offsets, lengths, sample_rate_in, sample_rate_out, target, out=out)
+
+
+def resample_packed(packed: torch.Tensor, offsets, lengths, sample_rate_in: int, sample_rate_out: int, target: int,
+                    out: torch.Tensor = None) -> torch.Tensor:
+    """``resample_clips`` on clips that already lie in one device buffer: clip ``b`` is ``packed[offsets[b] :
+    offsets[b] + lengths[b]]`` (host sequences; gaps between the clips, any alignment and overlaps are allowed --
+    nothing outside a clip's own samples is read).  Every (offset, length) is checked against the buffer on the host
+    (``ValueError``) before anything is launched."""
+    up, down, kmax = resample_plan(sample_rate_in, sample_rate_out)
+    if not packed.is_cuda:
+        raise RuntimeError("resample_packed runs on the MI355X kernels; move the packed clips to the GPU")
+    if packed.dtype != torch.float32 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous 1-D fp32 tensor")
+    offsets, lengths = [int(o) for o in offsets], [int(n) for n in lengths]
+    B, target, dev = len(offsets), int(target), packed.device
+    if len(lengths) != B or not B:
+        raise ValueError(f"{B} offsets for {len(lengths)} lengths")
+    if target < 0 or B > 65535:
+        raise ValueError(f"target {target} must not be negative, and at most 65535 clips go in one launch (got {B})")
+    for o, n in zip(offsets, lengths):
+        if o < 0 or n < 0 or o + n > int(packed.numel()):
+            raise ValueError(f"clip [{o}, {o + n}) reaches outside the packed buffer of {int(packed.numel())} samples")
+    if out is None:
+        out = torch.empty(B, target, device=dev, dtype=torch.float32)
+    elif tuple(out.shape) != (B, target) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"the resampler's out must be contiguous fp32 [{B}, {target}] on {dev}")
+    if target:
+        meta = _h2d(torch.tensor([offsets, lengths], dtype=torch.int64), dev)
+        K.LIB("mer_resample_clips", B, target, up, down, kmax, _polyphase(dev, up, down).data_ptr() if kmax else None,
+              packed.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), out.data_ptr(), K.stream_ptr())
+    return out
+
+
+AUDIO_SNRS_DB = (20.0, 15.0, 10.0)  # ravdess.py:533, the SNRs drawn at level in [0.5, 0.9); 5 dB above
+
+
+def draw_audio_augment(rng, target: int, n_noise: int) -> tuple:
+    """One clip's audio draws of ravdess.py:519-576 from a numpy Generator, in ``load_audio_wav``'s order:
+    ``uniform`` (the level), then ``choice`` of the SNR when ``0.5 <= level < 0.9`` (5 dB above, nothing below 0.5),
+    then ``integers`` for the start in the bar-noise track of ``n_noise`` samples (tiled when shorter than ``target``)
+    when ``max_start > 0``.  Returns ``(mode, start, snr_db, seed)`` for ``mix_noise_clips``: mode 0 leaves the clip
+    alone, 1 mixes the track in, 2 (``n_noise == 0``) is the Gaussian fallback, whose one draw is a 63-bit seed in
+    place of the host's ``rng.normal`` (the audio draws are an item's last, so nothing downstream shifts)."""
+    target, n = int(target), int(n_noise)
+    level = rng.uniform(0.0, 1.0)
+    if level < 0.5:
+        return 0, 0, 0.0, 0
+    snr_db = float(rng.choice(list(AUDIO_SNRS_DB))) if level < 0.9 else 5.0
+    if n > 0:
+        tiled = n if n >= target else n * (target // n + 1)
+        max_start = max(0, tiled - target)
+        start = int(rng.integers(0, max_start + 1)) if max_start > 0 else 0
+        return 1, start, snr_db, 0
+    return 2, 0, snr_db, int(rng.integers(0, 2 ** 63 - 1))
+
+
+def mix_noise_clips(wav: torch.Tensor, params: Sequence[tuple], bar_noise: torch.Tensor = None,
+                    return_scale: bool = False):
+    """The train-split noise mix (ravdess.py:539-576) of a waveform batch on the GPU: ``wav`` fp32 ``[B, target]`` or
+    ``[B, 1, target]`` + one ``draw_audio_augment`` tuple ``(mode, start, snr_db, seed)`` per clip -> a new tensor
+    of the same shape (mer_mix_noise_clips).
+
+    Mode 1: ``clip(wav + noise[(start + i) % n] * scale, -1, 1)`` with ``scale = sqrt(ps / max(10^(snr/10), 1e-8) /
+    pn)`` from the fp64 mean powers of the row and of the noise window (1 when ``pn <= 1e-8``), the host
+    ``data.mix_noise``'s rule.  Mode 2: Gaussian noise of that target power from the augmentation's hashed
+    ``normal_table`` draw per (seed, sample).  Mode 0: copied bit for bit, not clamped.  ``bar_noise``: the 16 kHz
+    track, 1-D fp32 on the device (``ClipLoader`` uploads it once).  The descriptors are validated here before any
+    launch.  ``return_scale=True`` also returns the ``[B]`` fp32 factors the device used (mode 2: sigma; mode 0: 0)."""
+    if wav.dtype != torch.float32 or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+        raise ValueError("wav must be fp32 [B, target] or [B, 1, target]")
+    B, target = int(wav.shape[0]), int(wav.shape[-1])
+    if len(params) != B:
+        raise ValueError(f"{len(params)} augmentation draws for {B} clips")
+    dev = wav.device
+    n_noise = 0
+    if bar_noise is not None:
+        if bar_noise.dtype != torch.float32 or bar_noise.dim() != 1 or bar_noise.device != dev:
+            raise ValueError(f"bar_noise must be a 1-D fp32 tensor on {dev}")
+        bar_noise = bar_noise.contiguous()
+        n_noise = int(bar_noise.numel())
+    for mode, start, snr_db, seed in params:
+        if mode not in (0, 1, 2):
+            raise ValueError(f"audio augmentation mode {mode!r}: 0 (none), 1 (noise track) or 2 (Gaussian)")
+        if mode == 1 and not n_noise:
+            raise ValueError("a mode-1 clip needs the bar-noise track")
+        if not 0 <= int(start) < 2 ** 62 or not 0 <= int(seed) < 2 ** 63 or not math.isfinite(float(snr_db)):
+            raise ValueError(f"bad audio augmentation draw (start {start}, snr_db {snr_db}, seed {seed})")
+    if not wav.is_cuda:
+        raise RuntimeError("mix_noise_clips runs on the MI355X kernels; move the waveforms to the GPU")
+    src = wav.contiguous()
+    out = torch.empty_like(src)
+    scale = torch.empty(B, device=dev, dtype=torch.float32)
+    if B and target:
+        ints = _h2d(torch.tensor([[int(m), int(s), int(sd)] for m, s, _, sd in params], dtype=torch.int64).t()
+                    .contiguous(), dev)
+        modes = ints[0].to(torch.int32)
+        snrs = _h2d(torch.tensor([float(s) for _, _, s, _ in params], dtype=torch.float32), dev)
+        parts = torch.empty(B, -(-target // 256), 2, device=dev, dtype=torch.float64)
+        K.LIB("mer_mix_noise_clips", B, target, src.data_ptr(), modes.data_ptr(), ints[1].data_ptr(), snrs.data_ptr(),
+              ints[2].data_ptr(), bar_noise.data_ptr() if n_noise else None, n_noise, _ztable(dev).data_ptr(),
+              parts.data_ptr(), scale.data_ptr(), out.data_ptr(), K.stream_ptr())
+    return (out, scale) if return_scale else out
+
+
+def assemble_waveforms(wavs: Sequence[torch.Tensor], sample_rates: Sequence[int], params: Sequence[tuple] = None,
+                       bar_noise: torch.Tensor = None, sample_rate: int = 16000, duration_sec: float = 3.0,
+                       device=None) -> torch.Tensor:
+    """``load_audio_wav`` after the decode, for a batch, on the GPU: decoded mono clips at their native rates ->
+    ``[B, 1, int(sample_rate * duration_sec)]``.  The batch is grouped by input rate: clips already at
+    ``sample_rate`` take the pad / crop kernel of ``pad_crop_waveforms``, every other rate one ``resample_clips``
+    launch; the rows land in batch order.  ``params`` (one ``draw_audio_augment`` tuple per clip, or None) then goes
+    through ``mix_noise_clips`` with the device track ``bar_noise``; with no clip to augment the mix is skipped.
+    Clips may be pre-sliced to ``resample_needed_inputs`` samples: the result is the same."""
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError("empty waveform batch")
+    if len(sample_rates) != len(wavs):
+        raise ValueError(f"{len(sample_rates)} sample rates for {len(wavs)} clips")
+    sr_out, target = int(sample_rate), int(sample_rate * duration_sec)
+    groups = {}
+    for i, sr in enumerate(sample_rates):
+        groups.setdefault(int(sr), []).append(i)
+    for sr in groups:
+        resample_plan(sr, sr_out)  # every refusal before any device work
+    dev = torch.device(device) if device is not None else next((w.device for w in wavs if w.is_cuda), None)
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("assemble_waveforms assembles the batch on the MI355X; pass device='cuda'")
+    if len(groups) == 1:
+        sr = next(iter(groups))
+        audio = pad_crop_waveforms(wavs, sr_out, duration_sec, device=dev) if sr == sr_out else \
+            resample_clips(wavs, sr, sr_out, target, device=dev).unsqueeze(1)
+    else:
+        audio = torch.empty(len(wavs), 1, target, device=dev, dtype=torch.float32)
+        for sr, idx in groups.items():
+            sub = [wavs[i] for i in idx]
+            rows = pad_crop_waveforms(sub, sr_out, duration_sec, device=dev)[:, 0] if sr == sr_out else \
+                resample_clips(sub, sr, sr_out, target, device=dev)
+            K.rows_scatter(rows, idx, audio.view(len(wavs), target))
+    if params is not None and any(p[0] for p in params):
+        audio = mix_noise_clips(audio, params, bar_noise)
+    return audio
 
 
 MEL_N_FFT, MEL_HOP, MEL_BINS, MEL_BINS_PAD = 400, 160, 201, 208

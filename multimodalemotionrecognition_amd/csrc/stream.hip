@@ -8,13 +8,10 @@
 // arrays); the kernels also clamp, so no launch reads or writes outside its buffers whatever the arrays hold.
 #include "common.h"
 #include "mer.h"
+#include "resample.h"
 
 namespace {
 
-constexpr int RS_BLOCK = 256;            // outputs per workgroup, one thread each
-constexpr long RS_MAX_SPAN = 12288;      // floats of LDS one workgroup may stage (48 KB)
-
-__host__ __device__ __forceinline__ long rs_half(long up, long down) { return 10 * (up > down ? up : down); }
 // outputs a stream of n inputs has emitted: every o whose newest input floor((o * down + half) / up) has arrived
 __host__ __device__ __forceinline__ long rs_emitted(long n, long up, long down) {
   if (up == 1 && down == 1) return n;
@@ -32,30 +29,20 @@ __device__ __forceinline__ float rs_input(long g, long n_in, int hist_len, const
   return j - hist_len < n_chunk ? chunk[j - hist_len] : 0.f;
 }
 
-// Output o = out0 + i: m = o * down + half is its centre in the upsampled stream, phase p = m % up, newest input
-// x = m / up; acc = sum over t < taps(p) of table[p][t] * input[x - t], t ascending (newest input first), one fmaf
-// per tap: the order and the operands depend on o alone, so any chunking gives the same bits.  The workgroup's
-// inputs [lo, lo + span) are staged in LDS.
+// Output o = out0 + i through rs_output (resample.h): its order and operands depend on o alone, so any chunking gives
+// the same bits.  The workgroup's inputs [lo, lo + span) are staged in LDS.
 __global__ __launch_bounds__(RS_BLOCK) void resample_stream_kernel(
     int up, int down, int kmax, const float* __restrict__ table, const float* __restrict__ chunk, long n_chunk,
     long n_in, long out0, long n_out, const float* __restrict__ hist, int hist_len, float* __restrict__ ring, long cap,
     int span) {
   extern __shared__ __attribute__((aligned(16))) float rs_lds[];
-  const long half = rs_half(up, down);
   const long i0 = (long)blockIdx.x * RS_BLOCK;
-  const long lo = ((out0 + i0) * down + half) / up - (kmax - 1);
+  const long lo = rs_lo(out0 + i0, up, down, kmax);
   for (int j = threadIdx.x; j < span; j += RS_BLOCK) rs_lds[j] = rs_input(lo + j, n_in, hist_len, hist, chunk, n_chunk);
   __syncthreads();
   const long i = i0 + threadIdx.x;
   if (i >= n_out) return;
-  const long m = (out0 + i) * down + half;
-  const long x = m / up;
-  const int p = (int)(m - x * up);
-  const int taps = (int)((2 * half - p) / up) + 1;  // taps k = p + t * up <= 2 * half
-  const float* __restrict__ h = table + (long)p * kmax;
-  int at = (int)(x - lo);  // < span: x <= the last output's newest input
-  float acc = 0.f;
-  for (int t = 0; t < taps && t < kmax; ++t, --at) acc = fmaf(h[t], at >= 0 && at < span ? rs_lds[at] : 0.f, acc);
+  const float acc = rs_output(out0 + i, up, down, kmax, table, rs_lds, lo, span);
   if (i >= n_out - cap) ring[(out0 + i) % cap] = acc;  // a chunk longer than the ring keeps its last cap outputs
 }
 
@@ -145,7 +132,7 @@ MER_API int mer_resample_stream(int up, int down, int kmax, const float* table, 
   // hist_len inputs reach back to the oldest input the next output can need: ceil(2 * half / up) <= kmax
   if (kmax != (int)(2 * half / up) + 1 || hist_len != kmax || !table || !hist || !hist_new || hist == hist_new)
     return (int)hipErrorInvalidValue;
-  const long span = (long)(RS_BLOCK - 1) * down / up + 1 + kmax;  // newest inputs of 256 outputs, plus kmax - 1 older
+  const long span = rs_span(up, down, kmax);
   if (span > RS_MAX_SPAN) return (int)hipErrorInvalidValue;
   if (n_out > 0) {
     const long blocks = (n_out + RS_BLOCK - 1) / RS_BLOCK;

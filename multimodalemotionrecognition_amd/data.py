@@ -14,7 +14,8 @@ code (``host/mer_io.cpp`` -> ``libmer_io.so``, C-ABI ``include/mer_io.h``) and t
   (ravdess.py:300-304).
 * ``ClipLoader`` -- the DataLoader of train.py for the GPU path: worker threads decode clips (the native calls
   release the GIL), each rank takes a disjoint shard (DP), and batches land in HBM as
-  ``[B, 8, 3, 112, 112]`` / ``[B, 1, 48000]`` / labels.
+  ``[B, 8, 3, 112, 112]`` / ``[B, 1, 48000]`` / labels.  ``device_audio=True`` leaves only the WAV decode and the
+  draws to the workers: resampling, pad / crop and the noise mix run on the device (``clips.assemble_waveforms``).
 """
 from __future__ import annotations
 
@@ -242,13 +243,21 @@ class ClipLoader:
     ``clips.augment_clips`` launch per batch with per-clip draws from the same generator; it is bit-exact against
     the restatement in ``oracle/clips_ref.py``, and parity against cv2 itself is unpinned (cv2 is absent here).
     ``audio_features="mel"``: ``audio`` is ``clips.log_mel`` of the waveform batch, ``[B, 1, n_mels, 301]`` (what the
-    mel ``AudioNet`` models take); the default ``"wav"`` yields the waveforms."""
+    mel ``AudioNet`` models take); the default ``"wav"`` yields the waveforms.
+
+    ``device_audio=True`` moves the audio work after the WAV decode to the GPU: a worker only decodes the file at its
+    native rate, slices it to the samples the kept outputs read (``clips.resample_needed_inputs``) and makes the
+    augmentation draws (``clips.draw_audio_augment``, the host's draws in the host's order); the batch then crosses
+    PCIe as one packed pinned copy per input rate and ``clips.assemble_waveforms`` resamples, pads / crops and mixes
+    the noise there (the track is uploaded once per loader).  Against the default it differs by the resampler's
+    rounding (fp32 fmaf sums against the host's double-rounded taps) and, with no bar-noise track, by the Gaussian
+    fallback's generator; video, labels and every draw are the same.  The default (``False``) is the host path."""
 
     def __init__(self, items: Sequence[Tuple], batch_size: int = 32, num_frames: int = 8, size: int = 112,
                  sample_rate: int = 16000, duration_sec: float = 3.0, rank: int = 0, world: int = 1,
                  workers: int = 8, prefetch: int = 2, device="cuda", shuffle: bool = False, seed: int = 0,
                  drop_last: bool = True, augment: bool = False, bar_noise: Optional[np.ndarray] = None,
-                 pad_shards: bool = True, audio_features: str = "wav", n_mels: int = 64):
+                 pad_shards: bool = True, audio_features: str = "wav", n_mels: int = 64, device_audio: bool = False):
         self.all_items = list(items)
         if audio_features not in ("wav", "mel"):
             raise ValueError(f"audio_features must be 'wav' or 'mel', got {audio_features!r}")
@@ -263,6 +272,10 @@ class ClipLoader:
         self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
         self.augment, self.bar_noise = bool(augment), bar_noise
         self.pad_shards = bool(pad_shards)
+        self.device_audio = bool(device_audio)
+        self._bar_dev = None  # the bar-noise track on the device, uploaded once (device_audio)
+        if self.device_audio and self.device.type != "cuda":
+            raise RuntimeError("ClipLoader(device_audio=True) runs on the MI355X kernels; pass device='cuda'")
         self.epoch = 0
 
     @property
@@ -285,18 +298,26 @@ class ClipLoader:
         # frames of one batch may differ in size (per-clip crops): resize each clip's frames on the device
         if self.augment:  # resized uint8 clips, then ONE augmentation + normalisation launch with per-clip draws
             u8 = torch.empty(len(decoded), self.T, self.size, self.size, 3, device=self.device, dtype=torch.uint8)
-            for i, (f, _, _, _, _) in enumerate(decoded):
-                clips.resize_frames_u8(torch.from_numpy(f).to(self.device), self.size, out=u8[i])
-            video = clips.augment_clips(u8, [va for _, _, _, _, va in decoded])
+            for i, d in enumerate(decoded):
+                clips.resize_frames_u8(torch.from_numpy(d[0]).to(self.device), self.size, out=u8[i])
+            video = clips.augment_clips(u8, [d[4] for d in decoded])
         else:
-            vids = [clips.preprocess_frames(torch.from_numpy(f).to(self.device), self.size) for f, _, _, _, _ in decoded]
+            vids = [clips.preprocess_frames(torch.from_numpy(d[0]).to(self.device), self.size) for d in decoded]
             video = torch.stack(vids).contiguous()
-        audio = clips.pad_crop_waveforms([torch.from_numpy(w) for _, w, _, _, _ in decoded], self.sr, self.dur,
-                                         device=self.device)
+        wavs = [torch.from_numpy(d[1]) for d in decoded]
+        if self.device_audio:  # native-rate clips: one packed pinned copy per rate, resample + pad / crop + mix there
+            if self.augment and self._bar_dev is None and self.bar_noise is not None and self.bar_noise.size:
+                track = np.ascontiguousarray(self.bar_noise, dtype=np.float32).reshape(-1)
+                self._bar_dev = clips._h2d(torch.from_numpy(track), self.device)
+            audio = clips.assemble_waveforms(wavs, [d[5][0] for d in decoded],
+                                             [d[5][1] for d in decoded] if self.augment else None, self._bar_dev,
+                                             self.sr, self.dur, device=self.device)
+        else:
+            audio = clips.pad_crop_waveforms(wavs, self.sr, self.dur, device=self.device)
         if self.audio_features == "mel":  # RavdessAVDataset's audio item (ravdess.py:607): [B, 1, n_mels, T]
             audio = clips.log_mel(audio, n_mels=self.n_mels, sample_rate=self.sr)
-        labels = torch.tensor([lab for _, _, lab, _, _ in decoded], dtype=torch.long).to(self.device)
-        return video, audio, labels, _collate_meta([m for _, _, _, m, _ in decoded])
+        labels = torch.tensor([d[2] for d in decoded], dtype=torch.long).to(self.device)
+        return video, audio, labels, _collate_meta([d[3] for d in decoded])
 
     def __iter__(self):
         order = shard_indices(len(self.all_items), self.rank, self.world, self.shuffle, self.seed, self.epoch,
@@ -345,6 +366,14 @@ class ClipLoader:
             rng = np.random.default_rng([self.seed, epoch, int(gi)]) if self.augment else None
             # the reference loads (and augments) the video before the audio (ravdess.py:639-645): same draw order
             vaug = clips.draw_video_augment(rng) if self.augment else None
+            if self.device_audio:  # decode at the native rate, keep what the kept outputs read, make the draws
+                wav, sr = read_wav_mono(wav_path)
+                target = int(self.sr * self.dur)
+                up, down, _ = clips.resample_plan(sr, self.sr)
+                wav = np.ascontiguousarray(wav[:clips.resample_needed_inputs(target, up, down)])
+                n_noise = int(self.bar_noise.size) if self.bar_noise is not None else 0
+                aaug = clips.draw_audio_augment(rng, target, n_noise) if self.augment else None
+                return frames, wav, int(label), meta, vaug, (int(sr), aaug)
             wav = load_audio_wav(wav_path, self.sr, self.dur, augment=self.augment, bar_noise=self.bar_noise,
                                  rng=rng)[0].numpy()
             return frames, wav, int(label), meta, vaug

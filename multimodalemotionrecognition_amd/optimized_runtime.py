@@ -147,7 +147,7 @@ class TorchModelRunner:
     def predict_timeline(self, frames_u8: Optional[torch.Tensor], waveform: Optional[torch.Tensor], fps, *,
                          window_sec: float = 3.0, hop_sec: float = 1.0, frames_per_window: int = 8,
                          frame_grid: str = "window", include_tail: bool = False, smooth_radius: int = 0,
-                         max_windows_per_batch: int = 64) -> Dict[str, Any]:
+                         max_windows_per_batch: int = 64, sample_rate: int = SAMPLE_RATE) -> Dict[str, Any]:
         """One prediction per window over a whole decoded recording, every frame encoded once.
 
         ``frames_u8`` ``[N, H, W, 3]`` uint8 RGB at ``fps`` and the mono 16 kHz ``waveform`` (fp32, any shape), host
@@ -164,11 +164,17 @@ class TorchModelRunner:
         Returns ``probs`` / ``smoothed`` ``[Nw, C]`` (``smoothed``: the centred moving average over ``2 *
         smooth_radius + 1`` windows, clipped to the recording), ``top1`` ``[Nw]`` int32 (argmax of ``smoothed``),
         ``starts_sec``, ``window_seconds``, ``labels``, ``num_windows``, ``num_unique_frames`` and ``num_frame_slots``
-        (``Nw * T``)."""
+        (``Nw * T``).
+
+        ``sample_rate``: the waveform's rate.  Any rate other than 16000 resamples the whole recording once on the
+        device (``clips.resample_clips``, scipy ``resample_poly``'s filter) before the windows are planned; the result
+        is ``predict_timeline`` of that resampled waveform.  At 16000 nothing changes."""
         from . import clips
         from . import kernels as K
         from .timeline import plan_windows
 
+        if int(sample_rate) != SAMPLE_RATE:
+            clips.resample_ratio(sample_rate, SAMPLE_RATE)  # refuses a non-positive rate before any device work
         if self.device.type != "cuda":
             raise RuntimeError("predict_timeline runs on the MI355X kernels; build the runner on a GPU device "
                                "(device='cuda')")
@@ -193,6 +199,9 @@ class TorchModelRunner:
         else:
             if waveform.dtype != torch.float32:
                 raise ValueError("waveform must be fp32")
+            if int(sample_rate) != SAMPLE_RATE:
+                waveform = clips.resample_clips(waveform.reshape(-1), int(sample_rate), SAMPLE_RATE,
+                                                device=self.device).reshape(-1)
             n_samples = int(waveform.numel())
         plan = plan_windows(n_frames, fps, n_samples, SAMPLE_RATE, window_sec, hop_sec,
                             frames_per_window if use_video else 1, frame_grid, include_tail)
@@ -267,11 +276,14 @@ def _result_row(runner: TorchModelRunner, row: torch.Tensor, top: Optional[int] 
 
 
 def process_recording(runner: TorchModelRunner, frames_u8: Optional[torch.Tensor], waveform: Optional[torch.Tensor],
-                      fps, **kw) -> List[Dict[str, Any]]:
+                      fps, *, sample_rate: int = SAMPLE_RATE, **kw) -> List[Dict[str, Any]]:
     """``process_batch`` over a whole recording: ``runner.predict_timeline(frames_u8, waveform, fps, **kw)`` as one
     dict per window in ``process_batch``'s format, plus the window's ``start_sec`` and ``window_seconds`` (the keys
     of the streaming session's result, streaming.py:103-115).  With ``smooth_radius > 0`` each dict also carries
-    ``smoothed``: the smoothed row in the same format, its top-1 the device's (lowest index on ties)."""
+    ``smoothed``: the smoothed row in the same format, its top-1 the device's (lowest index on ties).
+    ``sample_rate``: the waveform's rate; any rate other than 16000 is resampled once on the device."""
+    if int(sample_rate) != SAMPLE_RATE:
+        kw["sample_rate"] = int(sample_rate)
     res = runner.predict_timeline(frames_u8, waveform, fps, **kw)
     out = []
     for w, row in enumerate(res["probs"]):
