@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from tests.helpers import dropout_keep
+from tests.helpers import dropout_keep, dropout_keep_pair
 
 EPS32 = float(np.finfo(np.float32).eps)
 ERF_FAST_ABS = 1.5e-7  # csrc/common.h erf_fast: documented absolute error
@@ -61,12 +61,12 @@ def to_bf16(t) -> torch.Tensor:
     return t.to(F32).to(BF16)
 
 
-def bf16_interval(ref64, ref32):
+def bf16_interval(ref64, ref32, extra=0.0):
     """(lo, hi, tol): the bfloat16 values a kernel that stores bf16 may return, as float64 tensors.
-    tol = 16 max|ref32 - ref64| + eps32 max|ref64| is the float32 bar of assert_fp64_parity; lo / hi are the bf16
-    roundings of ref64 -/+ tol."""
+    tol = 16 max|ref32 - ref64| + eps32 max|ref64| (+ extra) is the float32 bar of assert_fp64_parity; lo / hi are the
+    bf16 roundings of ref64 -/+ tol."""
     assert ref64.dtype == F64 and ref32.dtype == F32 and tuple(ref64.shape) == tuple(ref32.shape)
-    tol = 16.0 * _max_abs(ref32.to(F64) - ref64) + EPS32 * _max_abs(ref64)
+    tol = 16.0 * _max_abs(ref32.to(F64) - ref64) + EPS32 * _max_abs(ref64) + float(extra)
     return to_bf16(ref64 - tol).to(F64), to_bf16(ref64 + tol).to(F64), tol
 
 
@@ -78,7 +78,7 @@ def bf16_determined(lo, hi, tol):
     return (hi - lo) <= 2 * tol * (1 + 2.0 ** -7)
 
 
-def assert_bf16_parity(got, ref64, ref32, what="", min_determined=0.9):
+def assert_bf16_parity(got, ref64, ref32, what="", min_determined=0.9, extra=0.0):
     """A kernel that stores bfloat16: every element must be the bf16 rounding of something within the float32 bar of
     the reference, bf16(ref64 - tol) <= got <= bf16(ref64 + tol) with tol = 16 max|ref32 - ref64| + eps32 max|ref64|.
     ``ref64`` / ``ref32`` are the restatement before its final rounding.  No bf16 tolerance appears: where no rounding
@@ -86,13 +86,14 @@ def assert_bf16_parity(got, ref64, ref32, what="", min_determined=0.9):
     bf16 is finer than tol (an exact zero) counts as determined too, see bf16_determined.  The eps32 term
     also covers the float32 step of the float64 -> bfloat16 conversion.  At least ``min_determined`` of the elements
     must be determined, else the check is blind; that is a condition on the inputs, not on the kernel
-    (tests/test_kernel_parity_cpu.py shows the restatements meet it).  Prints and returns err / bar like
-    assert_fp64_parity, with err the largest distance from ref64 at which a value rounds to the kernel's bf16 (0 where
-    got == bf16(ref64))."""
+    (tests/test_kernel_parity_cpu.py shows the restatements meet it).  ``extra`` is added to tol before the interval
+    is formed (the documented error of erf_fast under a GELU, as in assert_fp64_parity).  Prints and returns
+    err / bar like assert_fp64_parity, with err the largest distance from ref64 at which a value rounds to the
+    kernel's bf16 (0 where got == bf16(ref64))."""
     got = torch.as_tensor(got).detach().cpu()
     assert got.dtype == BF16, f"{what}: expected a bfloat16 output, got {got.dtype}"
     assert tuple(got.shape) == tuple(ref64.shape), (what, got.shape, ref64.shape)
-    lo, hi, tol = bf16_interval(ref64, ref32)
+    lo, hi, tol = bf16_interval(ref64, ref32, extra)
     det = bf16_determined(lo, hi, tol)
     share = float(det.double().mean()) if det.numel() else 1.0
     assert share >= min_determined, f"{what}: only {share:.1%} of the elements are determined, the check is blind"
@@ -141,7 +142,18 @@ def assert_dropout_parity(got, keep, p, ref64, ref32, extra=0.0, what=""):
     assert 2 * int(live.sum()) >= int(keep.sum()), f"{what}: too few kept values are non-zero, the mask check is blind"
     assert bool((got[~keep] == 0).all()) and bool((got[live] != 0).all()), \
         f"{what}: the kernel's zeros differ from the restated mask"
+    if got.dtype == BF16:  # a bf16 store: a live value is at least eps32 max|ref|, far above the smallest bf16
+        return assert_bf16_parity(got, ref64, ref32, extra=extra, what=what)
     return assert_fp64_parity(got, ref64, ref32, extra=extra, what=what)
+
+
+def keep_mask_pair(base, site, idx, p) -> torch.Tensor:
+    """keep_mask for the paired-index dropout of the WavLM encoder's sites (dropout_scale_pair / dropout_pairs: the
+    bf16 GEMM epilogues, mer_layernorm_tr, mer_dropout_rows)."""
+    idx = np.asarray(idx, dtype=np.uint64)
+    if p <= 0:
+        return torch.ones(idx.shape, dtype=torch.bool)
+    return torch.from_numpy(dropout_keep_pair(int(base), int(site), idx.reshape(-1), f32(p)).reshape(idx.shape))
 
 
 # ---- sentinels: outputs are views into wider / longer buffers whose every other element must stay untouched ----
@@ -231,6 +243,52 @@ class GuardedBf16:
             assert not bool(never.any()), f"{what}: {int(never.sum())} output elements never written"
         if not written:
             assert self._untouched(v), f"{what}: the output was written by a call that must refuse"
+
+
+class GuardedBf16Rows:
+    """A bfloat16 [rows, cols] output with row stride ld > cols inside a NaN-filled buffer, ``offset`` elements in (a
+    multiple of 8 keeps 16-byte vector stores aligned; an odd one forces a kernel's scalar path).  ``check`` requires
+    every pad element (in front, between the rows, behind) to still be NaN and every view element to have been
+    written; ``written=False``: the view too must be untouched (a call that refuses, a skipped layer)."""
+
+    def __init__(self, rows, cols, ld, device, offset=16, tail=16):
+        assert ld > cols
+        self.rows, self.cols, self.ld, self.offset = int(rows), int(cols), int(ld), int(offset)
+        span = (self.rows - 1) * self.ld + self.cols
+        self.buf = torch.full((self.offset + span + tail,), float("nan"), dtype=BF16, device=device)
+        self.view = self.buf.as_strided((self.rows, self.cols), (self.ld, 1), self.offset)
+        self.inside = torch.zeros(self.buf.numel(), dtype=torch.bool)
+        idx = self.offset + torch.arange(self.rows)[:, None] * self.ld + torch.arange(self.cols)[None, :]
+        self.inside[idx.reshape(-1)] = True
+
+    def check(self, what="", written=True):
+        nan = torch.isnan(self.buf.detach().cpu().float())
+        bad = ~nan & ~self.inside
+        assert not bool(bad.any()), f"{what}: {int(bad.sum())} pad elements outside the output view were overwritten " \
+                                    f"(first at flat index {int(bad.nonzero()[0]) if bool(bad.any()) else -1})"
+        never = nan & self.inside
+        if written:
+            assert not bool(never.any()), f"{what}: {int(never.sum())} output elements never written (or NaN)"
+        else:
+            assert bool(never[self.inside].all()), f"{what}: the output was written by a call that must leave it alone"
+
+
+def padded_input_bf16(t, ld, device, offset=0):
+    """bf16-valued ``t`` [rows, cols] as a bfloat16 device view with row stride ld >= cols whose gaps (and 8 elements
+    behind the last row) hold NaN.  ``offset`` elements in front: a multiple of 8 keeps the rows 16-byte aligned."""
+    rows, cols = t.shape
+    assert ld >= cols
+    buf = torch.full((offset + (rows - 1) * ld + cols + 8,), float("nan"), dtype=BF16, device=device)
+    view = buf.as_strided((rows, cols), (ld, 1), offset)
+    view.copy_(t.to(BF16).to(device))
+    assert bool((view.float().cpu() == t.to(F32)).all()), "the input is not bf16-representable"
+    return view
+
+
+def bf16_truncate(t) -> torch.Tensor:
+    """float -> bfloat16 by dropping the low 16 bits (the store a kernel must NOT do; the CPU mutation checks)."""
+    bits = t.to(F32).contiguous().view(torch.int32) & -65536
+    return bits.view(F32).to(BF16)
 
 
 # ---- seeded CPU inputs ----
@@ -523,6 +581,121 @@ def ref_rows_sum(rows, out0, dt):
     return {"out": tot if out0 is None else out0.to(dt) + tot}
 
 
+# ---- csrc/gemm_bf16.hip: the bf16 MFMA GEMM, its Conv1d 'rows' mode and the grouped positional conv ----
+def _act(z, act):
+    return torch.relu(z) if act == "relu" else (_gelu(z) if act == "gelu" else z)
+
+
+def gather_rows(buf, M, K, rpg, rstride, gstride):
+    """The A operand of rows mode: row m = buf[(m // rpg) * gstride + (m % rpg) * rstride : + K] of the flat buffer."""
+    m = torch.arange(M)
+    start = (m // rpg) * gstride + (m % rpg) * rstride
+    return buf.reshape(-1)[start[:, None] + torch.arange(K)[None, :]]
+
+
+def ref_gemm_bf16(a, w, bias, res, act, keep, p, dt):
+    """z = a w^T (+ bias); y = act(z); y *= keep / (1 - p) when p > 0; y += res -- the epilogue order of
+    csrc/gemm_bf16.hip (dropout after the activation, before the residual), before any final rounding."""
+    z = a.to(dt) @ w.to(dt).t()
+    if bias is not None:
+        z = z + bias.to(dt)
+    y = _act(z, act)
+    if p > 0:
+        y = y * drop_scale(keep, p, dt)
+    if res is not None:
+        y = y + res.to(dt)
+    return {"out": y, "z": z}
+
+
+def ref_posconv(x, wp, bias, res, act, B, L, C, G, taps, pad, dt):
+    """Grouped positional conv as the direct sum out[b, t, g cg + n] = act(sum_{tap, c} x[b, t + tap - pad, g cg + c]
+    wp[g, n, tap, c] + bias) + res with x zero outside [0, L); x [B, L, C], wp [G, cg, taps, cg]."""
+    cg = C // G
+    xp = torch.zeros(B, L + taps, G, cg, dtype=dt)
+    xp[:, pad:pad + L] = x.to(dt).reshape(B, L, G, cg)
+    wp = wp.to(dt).reshape(G, cg, taps, cg)
+    z = torch.zeros(B, L, G, cg, dtype=dt)
+    for tap in range(taps):
+        z = z + torch.einsum("blgc,gnc->blgn", xp[:, tap:tap + L], wp[:, :, tap, :])
+    z = z.reshape(B, L, C)
+    if bias is not None:
+        z = z + bias.to(dt)
+    y = _act(z, act)
+    if res is not None:
+        y = y + res.to(dt)
+    return {"out": y, "z": z}
+
+
+# ---- row kernels of the WavLM encoder and its stage-2 backward (csrc/wavlm.hip, csrc/wavlm_train.hip) ----
+def ref_layernorm(x, gamma, beta, eps, keep, p, dt):
+    """Row LayerNorm with optional dropout on its output."""
+    x = x.to(dt)
+    mean = x.mean(1, keepdim=True)
+    var = ((x - mean) ** 2).mean(1, keepdim=True)
+    y = (x - mean) / torch.sqrt(var + torch.tensor(f32(eps), dtype=dt)) * gamma.to(dt) + beta.to(dt)
+    return {"y": y * drop_scale(keep, p, dt) if p > 0 else y}
+
+
+LN_BWD_ROWS = 16  # csrc/wavlm_train.hip LN_ROWS: rows per block = rows per partial row
+
+
+def ref_ln_bwd(dys, x, gamma, eps, dt, block0=0):
+    """LayerNorm backward of g = sum(dys) on the saved input x: dx = rstd (g gamma - mean(g gamma) - xhat mean(g gamma
+    xhat)), and per block of 16 rows the partial rows part[blk] = (sum g xhat, sum g, sum dx) -> [nblk, 3, d].
+    ``block0`` shifts the blocks' first row (the CPU mutation check only)."""
+    x, gamma = x.to(dt), gamma.to(dt)
+    g = sum(t.to(dt) for t in dys)
+    mean = x.mean(1, keepdim=True)
+    rstd = 1 / torch.sqrt(((x - mean) ** 2).mean(1, keepdim=True) + torch.tensor(f32(eps), dtype=dt))
+    xh = (x - mean) * rstd
+    gg = g * gamma
+    dx = rstd * (gg - gg.mean(1, keepdim=True) - xh * (gg * xh).mean(1, keepdim=True))
+    rows = x.shape[0]
+    parts = []
+    for r0 in range(0, rows, LN_BWD_ROWS):
+        sl = slice(max(r0 + block0, 0), max(min(r0 + LN_BWD_ROWS, rows) + block0, 0))
+        parts.append(torch.stack([(g[sl] * xh[sl]).sum(0), g[sl].sum(0), dx[sl].sum(0)]))
+    return {"dx": dx, "part": torch.stack(parts)}
+
+
+def ref_fold_rows(part, out0, dt):
+    """out0 + sum_p part[p]."""
+    return {"out": out0.to(dt) + part.to(dt).sum(0)}
+
+
+def ref_colsum(x, out0, dt):
+    return {"out": out0.to(dt) + x.to(dt).sum(0)}
+
+
+def _gelu_grad(z):
+    return 0.5 * (1 + torch.erf(z * (0.5 ** 0.5))) + z * torch.exp(-0.5 * z * z) * (1 / math.sqrt(2 * math.pi))
+
+
+def ref_gelu(z, dt):
+    return {"f": _gelu(z.to(dt))}
+
+
+def ref_gelu_bwd(df, z, dbias0, dt):
+    """dz = df gelu'(z) before its bf16 rounding; dbias = dbias0 + column sums of the unrounded dz."""
+    dz = df.to(dt) * _gelu_grad(z.to(dt))
+    return {"dz": dz, "dbias": dbias0.to(dt) + dz.sum(0)}
+
+
+def ref_dropout_rows(x, keep, p, dt):
+    return {"y": x.to(dt) * drop_scale(keep, p, dt)}
+
+
+def ref_linear_wgrad(x, dy, dw0, col0, N, dt):
+    """dw0 + dy[:, col0:col0 + N]^T x."""
+    return {"dw": dw0.to(dt) + dy.to(dt)[:, col0:col0 + N].t() @ x.to(dt)}
+
+
+def ref_weightnorm_scale(v, g, dt):
+    """g[k] / ||v[:, :, k]||_2."""
+    v = v.to(dt)
+    return {"scale": g.to(dt) / torch.sqrt((v * v).sum((0, 1)))}
+
+
 # ======================================================================================================
 # One small seeded instance of every restatement (tests/test_kernel_parity_cpu.py checks that its float32
 # evaluation is a non-degenerate bar).  name -> fn(dt) -> dict of outputs.
@@ -622,6 +795,74 @@ def _instances():
     inst["avgpool"] = lambda dt: ref_avgpool(xp_, dya, dt)
     pr, o0 = randn(gb, 65, 40), randn(gb, 40)
     inst["rows_sum"] = lambda dt: ref_rows_sum(pr, o0, dt)
+    inst.update(_audio_instances())
+    return inst
+
+
+def gemm_bf16_inputs(M, N, K, seed, zsigma=0.8):
+    """bf16-valued A [M, K] (unit normal), W [N, K] scaled so that z = A W^T has sigma ``zsigma`` (a GELU output is
+    then determined at 90 % and more of its elements: DESIGN.md section 2), an fp32 bias and a bf16-valued residual."""
+    g = gen(seed)
+    return {"a": bf16_values(g, M, K), "w": bf16_values(g, N, K, scale=zsigma / math.sqrt(K)),
+            "bias": randn(g, N) * 0.5, "res": bf16_values(g, M, N)}
+
+
+def posconv_inputs(B, L, C, G, taps, seed, zsigma=0.8):
+    """x [B, L, C], wp [G, cg, taps, cg] (K-contiguous (tap, c) rows per output channel), bias, residual."""
+    g = gen(seed)
+    cg = C // G
+    return {"x": bf16_values(g, B, L, C), "wp": bf16_values(g, G, cg, taps, cg, scale=zsigma / math.sqrt(taps * cg)),
+            "bias": randn(g, C) * 0.5, "res": bf16_values(g, B, L, C)}
+
+
+def grid_index(*shape):
+    return np.arange(int(np.prod(shape)), dtype=np.uint64).reshape(shape)
+
+
+def _audio_instances():
+    """csrc/gemm_bf16.hip and the WavLM row kernels: one small instance per restatement."""
+    inst = {}
+    M, N, K = 37, 24, 64
+    gi = gemm_bf16_inputs(M, N, K, 20261101)
+    for act in ("none", "relu", "gelu"):
+        inst[f"gemm_bf16_{act}"] = lambda dt, act=act: ref_gemm_bf16(gi["a"], gi["w"], gi["bias"], gi["res"], act, None,
+                                                                     0.0, dt)
+    inst["gemm_bf16_gelu_plain"] = lambda dt: ref_gemm_bf16(gi["a"], gi["w"], None, None, "gelu", None, 0.0, dt)
+    kg = keep_mask_pair(BASE, SITE, grid_index(M, N), 0.1)
+    inst["gemm_bf16_gelu_drop"] = lambda dt: ref_gemm_bf16(gi["a"], gi["w"], gi["bias"], None, "gelu", kg, 0.1, dt)
+    # rows mode: Conv1d(k = 3, s = 2) over 2 clips of 9 frames of 64 channels
+    g = gen(20261102)
+    Lin, Cc = 9, 64
+    Lo = (Lin - 3) // 2 + 1
+    xr = bf16_values(g, 2 * Lin * Cc)
+    wr = bf16_values(g, N, 3 * Cc, scale=0.8 / math.sqrt(3 * Cc))
+    ar = gather_rows(xr, 2 * Lo, 3 * Cc, Lo, 2 * Cc, Lin * Cc)
+    inst["gemm_bf16_rows"] = lambda dt: ref_gemm_bf16(ar, wr, gi["bias"], None, "none", None, 0.0, dt)
+    pc = posconv_inputs(2, 17, 96, 2, 5, 20261103)
+    inst["posconv_gelu"] = lambda dt: ref_posconv(pc["x"], pc["wp"], pc["bias"], pc["res"], "gelu", 2, 17, 96, 2, 5, 2,
+                                                  dt)
+    inst["posconv_none"] = lambda dt: ref_posconv(pc["x"], pc["wp"], pc["bias"], None, "none", 2, 17, 96, 2, 5, 2, dt)
+    rows, d = 37, 256
+    xl, gam, bet = randn(g, rows, d) * 2 + 0.5, randn(g, d) * 0.3 + 1, randn(g, d) * 0.3
+    kl = keep_mask_pair(BASE, SITE, grid_index(rows, d), 0.1)
+    inst["layernorm"] = lambda dt: ref_layernorm(xl, gam, bet, 1e-5, None, 0.0, dt)
+    inst["layernorm_drop"] = lambda dt: ref_layernorm(xl, gam, bet, 1e-5, kl, 0.1, dt)
+    dya, dyb = randn(g, rows, d), randn(g, rows, d)
+    inst["ln_bwd"] = lambda dt: ref_ln_bwd([dya, dyb], xl, gam, 1e-5, dt)
+    parts, o0 = randn(g, 65, 33), randn(g, 33)
+    inst["fold_rows"] = lambda dt: ref_fold_rows(parts, o0, dt)
+    inst["colsum"] = lambda dt: ref_colsum(parts, o0, dt)
+    zb = to_bf16(gelu_z(8, 33, 5)).to(F32)
+    df, db0 = randn(g, 8, 33), randn(g, 33)
+    inst["gelu"] = lambda dt: ref_gelu(zb, dt)
+    inst["gelu_bwd"] = lambda dt: ref_gelu_bwd(df, zb, db0, dt)
+    xd = bf16_values(g, 9, 40)
+    kd = keep_mask_pair(BASE, SITE, grid_index(9, 40), 0.1)
+    inst["dropout_rows"] = lambda dt: ref_dropout_rows(xd, kd, 0.1, dt)
+    xw, dyw, dw0 = bf16_values(g, 37, 24), bf16_values(g, 37, 32), randn(g, 16, 24)
+    inst["linear_wgrad"] = lambda dt: ref_linear_wgrad(xw, dyw, dw0, 8, 16, dt)
+    vw, gw = randn(g, 5, 7, 5), randn(g, 5)
+    inst["weightnorm_scale"] = lambda dt: ref_weightnorm_scale(vw, gw, dt)
     return inst
 
 
@@ -633,4 +874,8 @@ INSTANCES = _instances()
 EXACT_OUTPUTS = {"add_ln_no_r": {"s"}, "maxpool": {"y", "arg", "dx"}, "bn_finalize_eval": {"mean"}}
 # Outputs the kernels store as bfloat16: judged by assert_bf16_parity.
 BF16_OUTPUTS = {"bn_apply": {"y"}, "bn_apply_res_relu": {"y"}, "bn_apply_resbn_relu": {"y"}, "bn_bwd": {"dx"},
-                "bn_bwd_running": {"dx"}, "maxpool": {"y", "dx"}, "avgpool": {"dx"}}
+                "bn_bwd_running": {"dx"}, "maxpool": {"y", "dx"}, "avgpool": {"dx"},
+                "gemm_bf16_none": {"out"}, "gemm_bf16_relu": {"out"}, "gemm_bf16_gelu": {"out"},
+                "gemm_bf16_gelu_plain": {"out"}, "gemm_bf16_gelu_drop": {"out"}, "gemm_bf16_rows": {"out"},
+                "posconv_gelu": {"out"}, "posconv_none": {"out"}, "layernorm": {"y"}, "layernorm_drop": {"y"},
+                "ln_bwd": {"dx"}, "gelu": {"f"}, "gelu_bwd": {"dz"}, "dropout_rows": {"y"}}

@@ -3,7 +3,10 @@ restatement is close to, and distinct from, its float64 reference, and ``assert_
 rejects a 1e-4 perturbation of it.  ``assert_bf16_parity`` accepts bf16(ref32), rejects one bf16 step of a determined
 element and anything outside the interval, and finds at least 90 % of every bf16 output determined.  The max pool's
 restatement takes the first maximum; csrc/common.h ``fdiv``, emulated in float32, is exact below 2^22 and first wrong
-at 2^23 + 7 for a divisor of 8."""
+at 2^23 + 7 for a divisor of 8.  For the bf16 GEMM and the WavLM row kernels (tests/test_gemm_bf16_parity_gpu.py,
+tests/test_wavlm_rows_kernels_gpu.py) the faults a loose bar would let through are applied to the float32 restatement
+and must be rejected: a dropped K chunk, swapped bias columns, the residual before the activation, dropout after the
+residual, a truncating bf16 store, a shifted tap, an ``ln_bwd`` partial row over the wrong rows."""
 import numpy as np
 import pytest
 import torch
@@ -170,6 +173,147 @@ def test_guarded_bf16_detects_unwritten_and_outside_writes():
     g.view[0].fill_(1.0)
     with pytest.raises(AssertionError, match="never written"):
         g.check("half written")
+
+
+def test_guarded_bf16_rows_detects_pad_writes_and_unwritten_elements():
+    g = kp.GuardedBf16Rows(3, 5, 8, "cpu")
+    assert tuple(g.view.shape) == (3, 5) and g.view.stride() == (8, 1) and g.view.storage_offset() == 16
+    g.check("refused call", written=False)
+    with pytest.raises(AssertionError, match="never written"):
+        g.check("nothing written")
+    g.view[:2].fill_(1.0)
+    with pytest.raises(AssertionError, match="never written"):
+        g.check("last row missing")
+    with pytest.raises(AssertionError, match="must leave it alone"):
+        g.check("refused call", written=False)
+    g.view.fill_(1.0)
+    g.check("written")
+    g.buf[16 + 5] = 0.0  # the first pad element of row 0
+    with pytest.raises(AssertionError, match="outside the output view"):
+        g.check("pad write")
+    odd = kp.GuardedBf16Rows(2, 4, 7, "cpu", offset=17)
+    assert odd.view.storage_offset() == 17
+    odd.view.fill_(2.0)
+    odd.check("odd offset")
+    odd.buf[16] = 1.0
+    with pytest.raises(AssertionError, match="outside the output view"):
+        odd.check("write in front")
+
+
+def test_padded_input_bf16_has_nan_gaps():
+    t = kp.bf16_values(kp.gen(1), 3, 5)
+    v = kp.padded_input_bf16(t, 8, "cpu", offset=8)
+    assert v.dtype == torch.bfloat16 and v.stride() == (8, 1) and bool((v.float() == t).all())
+    whole = v.as_strided((8 + 2 * 8 + 5 + 8,), (1,), 0).float()
+    inside = torch.zeros(whole.numel(), dtype=torch.bool)
+    inside[(8 + torch.arange(3)[:, None] * 8 + torch.arange(5)[None, :]).reshape(-1)] = True
+    assert bool(torch.isnan(whole[~inside]).all()) and not bool(torch.isnan(whole[inside]).any())
+    with pytest.raises(AssertionError, match="bf16-representable"):
+        kp.padded_input_bf16(t + 2.0 ** -12, 8, "cpu")
+
+
+def test_bf16_parity_extra_widens_tol_before_the_interval():
+    ref64 = torch.tensor([1.0 + 2.0 ** -8 - 1e-5] + [1.001 + 2.0 ** -7 * k for k in range(19)], dtype=torch.float64)
+    ref32 = (ref64 + 1e-7).float()
+    up = kp.to_bf16(ref64)
+    up[0] = 1.0 + 2.0 ** -7  # the boundary is 1e-5 above the reference: out of reach of tol ~ 1.7e-6 ...
+    with pytest.raises(AssertionError, match="outside the bf16 interval"):
+        kp.assert_bf16_parity(up, ref64, ref32, what="no extra")
+    kp.assert_bf16_parity(up, ref64, ref32, what="extra", extra=2e-5)  # ... and within reach of tol + extra
+    assert kp.bf16_interval(ref64, ref32, 2e-5)[2] == pytest.approx(kp.bf16_interval(ref64, ref32)[2] + 2e-5)
+
+
+# ---- mutations of the float32 restatements that the GPU tests' assertions must reject ----
+def _rejected_both_ways(bad32, ref64, ref32, what):
+    """As an fp32 output (assert_fp64_parity) and as a correctly rounded bf16 output (assert_bf16_parity)."""
+    with pytest.raises(AssertionError):
+        kp.assert_fp64_parity(bad32, ref64, ref32, what=f"{what} fp32")
+    with pytest.raises(AssertionError, match="outside the bf16 interval"):
+        kp.assert_bf16_parity(kp.to_bf16(bad32), ref64, ref32, what=f"{what} bf16")
+
+
+GEMM_MUT = [(37, 24, 64, 0.8, 11), (130, 72, 2048, 0.8, 12), (45, 40, 1536, 0.05 * 1536 ** 0.5, 13)]
+
+
+@pytest.mark.parametrize("M,N,K,zsigma,seed", GEMM_MUT)
+@pytest.mark.parametrize("act", ["none", "relu", "gelu"])
+def test_gemm_bf16_mutations_are_rejected(M, N, K, zsigma, seed, act):
+    """The last shape has W scaled by 0.05 as the Conv1d case of tests/test_wavlm_gpu.py: a dropped chunk is small."""
+    i = kp.gemm_bf16_inputs(M, N, K, seed, zsigma=zsigma)
+    a, w, bias, res = i["a"], i["w"], i["bias"], i["res"]
+    ref64 = kp.ref_gemm_bf16(a, w, bias, res, act, None, 0.0, kp.F64)["out"]
+    ref32 = kp.ref_gemm_bf16(a, w, bias, res, act, None, 0.0, kp.F32)["out"]
+    kp.assert_fp64_parity(ref32, ref64, ref32, what="unmutated")
+    kp.assert_bf16_parity(kp.to_bf16(ref32), ref64, ref32, what="unmutated bf16")
+    # one 8-wide K chunk of one row dropped
+    rng = np.random.default_rng(seed)
+    r, c = int(rng.integers(M)), int(rng.integers(K // 8))
+    a2 = a.clone()
+    a2[r, 8 * c:8 * c + 8] = 0
+    _rejected_both_ways(kp.ref_gemm_bf16(a2, w, bias, res, act, None, 0.0, kp.F32)["out"], ref64, ref32, "K chunk")
+    # two bias columns swapped
+    b2 = bias.clone()
+    b2[[3, 4]] = bias[[4, 3]]
+    _rejected_both_ways(kp.ref_gemm_bf16(a, w, b2, res, act, None, 0.0, kp.F32)["out"], ref64, ref32, "bias swap")
+    # the residual added before the activation (the same thing for act none)
+    if act != "none":
+        z32 = kp.ref_gemm_bf16(a, w, bias, None, "none", None, 0.0, kp.F32)["out"]
+        _rejected_both_ways(kp._act(z32 + res, act), ref64, ref32, "residual before act")
+    # the final store truncated instead of rounded to nearest even
+    with pytest.raises(AssertionError, match="outside the bf16 interval"):
+        kp.assert_bf16_parity(kp.bf16_truncate(ref32), ref64, ref32, what="truncating store")
+
+
+def test_dropout_before_the_activation_or_after_the_residual_is_rejected():
+    M, N, K, p = 37, 24, 64, 0.1
+    i = kp.gemm_bf16_inputs(M, N, K, 14)
+    keep = kp.keep_mask_pair(kp.BASE, kp.SITE, kp.grid_index(M, N), p)
+    assert 0 < int((~keep).sum()) < M * N // 4
+    ref64 = kp.ref_gemm_bf16(i["a"], i["w"], i["bias"], i["res"], "gelu", keep, p, kp.F64)["out"]
+    ref32 = kp.ref_gemm_bf16(i["a"], i["w"], i["bias"], i["res"], "gelu", keep, p, kp.F32)["out"]
+    assert bool((ref32[~keep] == i["res"][~keep]).all())  # a dropped element is its residual, exactly
+    after = kp.ref_gemm_bf16(i["a"], i["w"], i["bias"], i["res"], "gelu", None, 0.0, kp.F32)["out"] * \
+        kp.drop_scale(keep, p, kp.F32)
+    _rejected_both_ways(after, ref64, ref32, "dropout after the residual")
+    # the single-index mask (the xattn head's) instead of the paired one
+    other = kp.keep_mask(kp.BASE, kp.SITE, kp.grid_index(M, N), p)
+    assert not bool((other == keep).all())
+
+
+def test_posconv_restatement_is_the_grouped_conv1d_and_rejects_a_shifted_tap():
+    B, L, C, G, taps, pad = 2, 17, 96, 2, 5, 2
+    cg = C // G
+    i = kp.posconv_inputs(B, L, C, G, taps, 15)
+    ref64 = kp.ref_posconv(i["x"], i["wp"], i["bias"], i["res"], "gelu", B, L, C, G, taps, pad, kp.F64)
+    ref32 = kp.ref_posconv(i["x"], i["wp"], i["bias"], i["res"], "gelu", B, L, C, G, taps, pad, kp.F32)
+    w = i["wp"].reshape(C, taps, cg).permute(0, 2, 1).double()  # Conv1d's [Cout][Cin / G][k]
+    z = torch.nn.functional.conv1d(i["x"].double().transpose(1, 2), w, i["bias"].double(), padding=pad, groups=G)
+    assert float((z.transpose(1, 2)[:, :L] - ref64["z"]).abs().max()) < 1e-12
+    shifted = kp.ref_posconv(i["x"], i["wp"], i["bias"], i["res"], "gelu", B, L, C, G, taps, pad + 1, kp.F32)["out"]
+    _rejected_both_ways(shifted, ref64["out"], ref32["out"], "pad + 1")
+
+
+def test_ln_bwd_partial_row_over_the_wrong_rows_is_rejected():
+    g = kp.gen(16)
+    rows, d = 37, 256
+    x, gamma, dy = kp.randn(g, rows, d) * 2 + 0.5, kp.randn(g, d) * 0.3 + 1, kp.randn(g, rows, d)
+    ref64, ref32 = (kp.ref_ln_bwd([dy], x, gamma, 1e-5, dt) for dt in (kp.F64, kp.F32))
+    assert tuple(ref64["part"].shape) == (3, 3, d)
+    assert float((ref64["part"][:, 1].sum(0) - dy.double().sum(0)).abs().max()) < 1e-12  # dbeta = sum dy
+    shifted = kp.ref_ln_bwd([dy], x, gamma, 1e-5, kp.F32, block0=-1)["part"]
+    for q in range(3):  # partial row 1 (dgamma, dbeta or sum dx) over rows 15..30 instead of 16..31
+        bad = ref32["part"].clone()
+        bad[1, q] = shifted[1, q]
+        with pytest.raises(AssertionError):
+            kp.assert_fp64_parity(bad[1, q], ref64["part"][1, q], ref32["part"][1, q], what=f"ln_bwd part 1 / {q}")
+    kp.assert_fp64_parity(ref32["part"][1], ref64["part"][1], ref32["part"][1], what="ln_bwd part 1")
+
+
+def test_gather_rows_is_the_conv1d_window():
+    x = torch.arange(2 * 9 * 4, dtype=torch.float32)
+    a = kp.gather_rows(x, 2 * 4, 12, 4, 8, 36)  # k = 3, s = 2, C = 4, Lin = 9 -> Lout = 4
+    assert a[0].tolist() == list(range(12)) and a[1].tolist() == list(range(8, 20))
+    assert a[4].tolist() == list(range(36, 48)) and a[7].tolist() == list(range(60, 72))
 
 
 def test_ref_maxpool_takes_the_first_maximum_in_tap_order():
