@@ -195,6 +195,50 @@ int mer_vec_sum(int n, const float* x, float* out, int accumulate, void* stream)
 int mer_adam_step(long n, float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps,
                   float wd, int step, float grad_scale, void* stream);
 
+/* ---- gradient clipping and weight EMA over FusedAdam's flat buffers (csrc/optim.hip) ----
+ *
+ * mer_grad_sqnorm: partials[c] = sum of squares (fp64) of chunk c of a table of `nseg` segments.
+ *   segs: DEVICE int64[nseg][3] = (address of the segment's first float, its length n in floats, the index of its
+ *   first chunk); every segment is 16-byte aligned with n % 4 == 0 and n > 0, a segment owns ceil(n / MER_NORM_CHUNK)
+ *   chunks cut from ITS start, first chunks are the running sum of those counts and nchunks is their total.
+ *   Squares and sums are fp64 in a fixed order (csrc/optim.hip); partials[c] has one writer and no atomics, so the
+ *   result depends on neither the grid size nor the order in which workgroups run.  partials: double[nchunks]. */
+#define MER_NORM_CHUNK 4096
+int mer_grad_sqnorm(int nseg, const long* segs, long nchunks, double* partials, void* stream);
+
+/* mer_clip_finalize: one workgroup of MER_CLIP_THREADS threads adds partials[0 .. nchunks) in fp64 (thread t takes
+ * t, t + MER_CLIP_THREADS, ... in index order, then the fixed wave / LDS tree of mer_grad_sqnorm) and updates the
+ * fp32 record rec[MER_CLIP_REC_FLOATS]:
+ *   [MER_CLIP_TOTAL_NORM] total_norm = fp32(grad_scale * sqrt(sum)) of this call (the telemetry's "last"),
+ *   [MER_CLIP_COEF]       coef = min(1, max_norm / (total_norm + 1e-6f)) in fp32 -- torch's clip_grad_norm_ with
+ *                         error_if_nonfinite=False: a NaN norm gives a NaN coefficient, an infinite one gives 0,
+ *   [MER_CLIP_STEPS]      += 1 on every call,
+ *   [MER_CLIP_NORM_SUM]   += total_norm and
+ *   [MER_CLIP_NORM_MAX]   = max(itself, total_norm) on the calls whose total_norm is finite ONLY,
+ *   [MER_CLIP_NONFINITE]  += 1 on the calls whose total_norm is inf or NaN (such a norm enters neither the sum nor
+ *                         the max, so mean = NORM_SUM / (STEPS - NONFINITE) stays meaningful),
+ *   [6], [7]              reserved, never written.
+ * The four counters are fp32 (exact up to 2^24 calls) and are zeroed by the caller to start a new window; one thread
+ * updates them with plain loads and stores -- launches on one stream are ordered, no atomics are needed. */
+#define MER_CLIP_THREADS 256
+#define MER_CLIP_REC_FLOATS 8
+#define MER_CLIP_TOTAL_NORM 0
+#define MER_CLIP_COEF 1
+#define MER_CLIP_STEPS 2
+#define MER_CLIP_NORM_SUM 3
+#define MER_CLIP_NORM_MAX 4
+#define MER_CLIP_NONFINITE 5
+int mer_clip_finalize(long nchunks, const double* partials, float grad_scale, float max_norm, float* rec,
+                      void* stream);
+
+/* mer_adam_step with two nullable DEVICE pointers.  coef: one float (the record's [MER_CLIP_COEF]); the gradient is
+ * scaled by grad_scale * *coef, formed once per thread.  ema with ema_decay d: after the parameter update
+ * e += (1 - d) * (p_new - e).  With *coef == 1 (or coef NULL) and ema NULL the results are bit-identical to
+ * mer_adam_step.  p, g, m, v and ema 16-byte aligned; any n (4-wide body, scalar tail). */
+int mer_adam_step_ex(long n, float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps,
+                     float wd, int step, float grad_scale, const float* coef, float* ema, float ema_decay,
+                     void* stream);
+
 /* ============================ encoders (bf16 MFMA) ============================ */
 
 /* C[m,n] = act(sum_k A(m,k) W[n,k] + bias[n]) (+ R[m,n]), bf16 operands, fp32 accumulate, C bf16 (c_dtype=1)

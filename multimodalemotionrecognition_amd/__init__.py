@@ -21,9 +21,12 @@ def __getattr__(name):
         from . import audio
         return getattr(audio, name)
     # the validation loop and the per-stage epoch driver (src/train.py:247-301, 736-768, 1066-1150; src/eval.py)
-    if name in {"evaluate", "fit", "cosine_scheduler"}:
+    if name in {"evaluate", "fit", "cosine_scheduler", "load_training_state"}:
         from . import train
         return getattr(train, name)
+    if name == "FusedAdam":
+        from .optim import FusedAdam
+        return FusedAdam
     if name == "EvalMetrics":
         from .metrics import EvalMetrics
         return EvalMetrics
@@ -42,4 +45,4 @@ def __getattr__(name):
 
 __all__ = ["LIB", "MerKernelError", "available", "lib_path", "FusionModel", "VideoNet", "WavLMAudioEncoder",
            "AudioNet", "AudioCNN", "AudioResNet18", "SpecAugment", "evaluate", "fit", "cosine_scheduler", "EvalMetrics", "evaluate_checkpoint",
-           "plan_windows", "WindowPlan", "process_recording"]
+           "plan_windows", "WindowPlan", "process_recording", "FusedAdam", "load_training_state"]

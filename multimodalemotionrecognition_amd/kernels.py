@@ -359,6 +359,60 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale=1.0):
         float(b2), float(eps), float(wd), int(step), float(grad_scale), stream_ptr())
 
 
+NORM_CHUNK = 4096        # MER_NORM_CHUNK (include/mer.h): floats per chunk of mer_grad_sqnorm
+CLIP_THREADS = 256       # MER_CLIP_THREADS: threads of mer_clip_finalize's one workgroup
+CLIP_REC_FLOATS = 8      # MER_CLIP_REC_FLOATS and the record's indices
+CLIP_TOTAL_NORM, CLIP_COEF, CLIP_STEPS, CLIP_NORM_SUM, CLIP_NORM_MAX, CLIP_NONFINITE = range(6)
+
+
+class NormSegments:
+    """The device segment table of ``grad_sqnorm`` over the given fp32 tensors (each contiguous, 16-byte aligned, a
+    positive multiple of 4 elements) and the fp64 partials buffer of its chunks.  Building it copies the table to the
+    device; FusedAdam builds one per run layout and keeps it, so a steady-state step copies nothing.  The tensors'
+    storage must stay alive as long as the table is used (the table holds raw addresses)."""
+
+    def __init__(self, tensors):
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError("grad_sqnorm needs at least one segment")
+        rows, chunk0 = [], 0
+        for t in tensors:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("grad_sqnorm segments are contiguous fp32 tensors")
+            n = t.numel()
+            if n <= 0 or n % 4 or t.data_ptr() % 16:
+                raise ValueError("grad_sqnorm segments are 16-byte aligned with a positive multiple of 4 elements")
+            rows.append((t.data_ptr(), n, chunk0))
+            chunk0 += (n + NORM_CHUNK - 1) // NORM_CHUNK
+        dev = tensors[0].device
+        self.nseg, self.nchunks = len(rows), chunk0
+        self.table = torch.tensor(rows, dtype=torch.int64, device=dev)
+        self.partials = torch.zeros(chunk0, dtype=torch.float64, device=dev)
+
+
+def grad_sqnorm(segs: NormSegments):
+    """segs.partials[c] = fp64 sum of squares of chunk c (deterministic, independent of the grid)."""
+    LIB("mer_grad_sqnorm", segs.nseg, segs.table.data_ptr(), segs.nchunks, segs.partials.data_ptr(), stream_ptr())
+
+
+def clip_finalize(segs: NormSegments, grad_scale, max_norm, rec):
+    """rec (fp32[CLIP_REC_FLOATS], include/mer.h): total_norm, coef and the running telemetry."""
+    if rec.dtype != torch.float32 or rec.numel() < CLIP_REC_FLOATS or not rec.is_contiguous():
+        raise ValueError("the clip record is a contiguous fp32 tensor of CLIP_REC_FLOATS elements")
+    LIB("mer_clip_finalize", segs.nchunks, segs.partials.data_ptr(), float(grad_scale), float(max_norm),
+        rec.data_ptr(), stream_ptr())
+
+
+def adam_step_ex(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale=1.0, coef=None, ema=None, ema_decay=0.0):
+    """``adam_step`` with the clip coefficient read from the device (``coef``: a one-element fp32 tensor or None)
+    and an optional EMA plane updated after the parameters."""
+    if ema is not None and ema.numel() != p.numel():
+        raise ValueError("the EMA plane must match the parameters")
+    LIB("mer_adam_step_ex", p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), float(lr), float(b1),
+        float(b2), float(eps), float(wd), int(step), float(grad_scale), None if coef is None else coef.data_ptr(),
+        None if ema is None else ema.data_ptr(), float(ema_decay), stream_ptr())
+
+
 def _aligned16(*ts):
     for t in ts:
         if t is not None and t.data_ptr() % 16:

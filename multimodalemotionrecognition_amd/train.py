@@ -10,6 +10,8 @@
   the device (``metrics.EvalMetrics``), read once per evaluation.
 * ``cosine_scheduler`` / ``fit`` -- train.py:736-768 and the epoch loop of train.py:1071-1150 for one stage
   (validate, step the schedule, keep the best checkpoint, stop early).
+* ``save_checkpoint`` / ``load_training_state`` -- the reference's checkpoint file, optionally with the optimizer's
+  state (moments, step counts, weight EMA) so a run can be resumed.
 """
 from __future__ import annotations
 
@@ -103,15 +105,17 @@ def _backward_order(model: nn.Module, params):
     return sorted(params, key=rank)  # stable: module order inside each rank
 
 
-def build_optimizer(model: nn.Module, lr: float = 1e-3, weight_decay: float = 1e-4) -> FusedAdam:
+def build_optimizer(model: nn.Module, lr: float = 1e-3, weight_decay: float = 1e-4,
+                    max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None) -> FusedAdam:
     """train.py:899-902: Adam over every requires_grad parameter.  Parameters the configured mode never reaches
     (``FusionModel.unused_parameters``: audio_time_conv, the encoders' classifiers under xattn ...) get no
     gradient in the reference, so its Adam skips them on every step; they are left out of the flat buffers
-    (and the data-parallel all-reduce) here, which is the same update."""
+    (and the data-parallel all-reduce) here, which is the same update.  ``max_grad_norm`` / ``ema_decay``: device-side
+    gradient clipping and weight averaging (``FusedAdam``); off by default, as in the reference."""
     params = build_optimizer_param_order(model)
     if not params:
         raise RuntimeError("No trainable parameters found for optimizer.")
-    return FusedAdam(params, lr=lr, weight_decay=weight_decay)
+    return FusedAdam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
 
 
 def build_optimizer_param_order(model: nn.Module):
@@ -168,7 +172,9 @@ def apply_two_stage_freeze_policy(model: FusionModel, stage: int, unfreeze_wavlm
 
 
 def build_fusion_stage_optimizer(model: nn.Module, stage: int, lr: float = 1e-3, audio_backbone_lr: float = 1e-5,
-                                 video_backbone_lr: float = 1e-5, weight_decay: float = 1e-4) -> FusedAdam:
+                                 video_backbone_lr: float = 1e-5, weight_decay: float = 1e-4,
+                                 max_grad_norm: Optional[float] = None,
+                                 ema_decay: Optional[float] = None) -> FusedAdam:
     """train.py:831-872: param groups fusion@lr, audio@audio_backbone_lr, video@video_backbone_lr."""
     fusion, audio, video = [], [], []
     dead = {id(q) for q in getattr(model, "unused_parameters", lambda: [])()}
@@ -189,7 +195,7 @@ def build_fusion_stage_optimizer(model: nn.Module, stage: int, lr: float = 1e-3,
             raise RuntimeError("Stage-2 expects trainable parameters, but none are trainable.")
     else:
         raise ValueError(f"Unsupported optimizer stage: {stage}")
-    return FusedAdam(groups, lr=lr, weight_decay=weight_decay)
+    return FusedAdam(groups, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
 
 def make_loss(fusion_mode: str, label_smoothing: float = 0.0) -> nn.Module:
     """train.py:1030-1033."""
@@ -257,7 +263,9 @@ def train_one_epoch(model: nn.Module, loader, optimizer: FusedAdam, device: torc
     ``loader`` yields the reference's ``(video, audio, labels, meta)`` batches (ravdess.py:616, 654 through a
     DataLoader; ``data.ClipLoader`` yields the same); ``(video, audio, labels)`` is accepted too.  One batch of
     lookahead: the next batch's waveform starts its frozen-encoder forward during this step (TrainStep
-    ``next_audio``), which changes no result."""
+    ``next_audio``), which changes no result.  When the optimizer clips (``FusedAdam(max_grad_norm=...)``) the
+    metrics also carry ``grad_norm`` (mean over the epoch's finite norms), ``grad_norm_max`` and
+    ``nonfinite_steps``, read from the device once after the last step."""
     step = TrainStep(model, optimizer, loss_fn, fusion_mode, grad_sync, fusion_align_weight=fusion_align_weight)
     losses, cls_losses, con_losses, preds, targets = [], [], [], [], []
     n = 0
@@ -291,8 +299,12 @@ def train_one_epoch(model: nn.Module, loader, optimizer: FusedAdam, device: torc
     cls_total = float(torch.stack(cls_losses).sum().cpu()) / max(n, 1)
     con_total = float(torch.stack(con_losses).sum().cpu()) / max(n, 1) if con_losses else 0.0
     acc = float((preds_t == targets_t).float().mean()) if n else 0.0
-    return {"loss": total, "cls_loss": cls_total, "contrastive_loss": con_total, "acc": acc,
-            "f1": macro_f1(preds_t, targets_t)}
+    metrics = {"loss": total, "cls_loss": cls_total, "contrastive_loss": con_total, "acc": acc,
+               "f1": macro_f1(preds_t, targets_t)}
+    if getattr(optimizer, "max_grad_norm", None) is not None:
+        norms = optimizer.grad_norm_stats(reset=True)
+        metrics.update(grad_norm=norms["mean"], grad_norm_max=norms["max"], nonfinite_steps=norms["nonfinite_steps"])
+    return metrics
 
 
 def macro_f1(preds: torch.Tensor, targets: torch.Tensor) -> float:
@@ -377,14 +389,22 @@ def cosine_scheduler(optimizer, epochs_in_stage: int) -> torch.optim.lr_schedule
 def fit(model: nn.Module, train_loader, val_loader, optimizer, device, loss_fn: nn.Module, fusion_mode: str,
         epochs: int, *, fusion_align_weight: float = 0.0, scheduler=None, early_stopping_patience: int = 10,
         checkpoint_path=None, config: Optional[dict] = None, grad_sync: Optional[GradAllReduce] = None, group=None,
-        best_f1: float = -1.0) -> dict:
+        best_f1: float = -1.0, ema_eval: bool = False, save_optimizer: bool = False, start_epoch: int = 0) -> dict:
     """The epoch loop of train.py:1071-1150 for ONE stage: per epoch ``train_one_epoch``, ``evaluate``, then
     ``scheduler.step()``; on a strict improvement of the validation F1 the checkpoint is written (rank 0 only when
     distributed) and the patience counter reset, otherwise the epoch is counted and the loop stops once
     ``early_stopping_patience > 0`` epochs went by without one.  The two-stage switch stays with the caller: call
     ``fit`` once per stage (``apply_two_stage_freeze_policy`` / ``build_fusion_stage_optimizer``), passing the
     returned ``best_f1`` on.  ``train_one_epoch`` / ``evaluate`` / ``save_checkpoint`` are looked up as module
-    globals at call time."""
+    globals at call time.
+
+    ``ema_eval``: validate and checkpoint the optimizer's averaged weights (``FusedAdam(ema_decay=...)``): both run
+    inside ONE ``optimizer.ema_weights()`` per epoch.  ``save_optimizer``: the checkpoint also carries ``"optimizer"``, ``"epoch"``
+    and ``"best_f1"``, which ``load_training_state`` reads back; continue such a run with ``start_epoch`` (the epochs
+    already done: the loop runs ``start_epoch + 1 .. epochs``) and ``best_f1`` from its result.  The learning-rate
+    schedule is the caller's to restore."""
+    import contextlib
+
     import torch.distributed as td
 
     from . import dist as D
@@ -392,20 +412,26 @@ def fit(model: nn.Module, train_loader, val_loader, optimizer, device, loss_fn: 
     g = globals()
     best_f1, best_epoch, stale, stopped = float(best_f1), None, 0, False
     history = []
-    for epoch in range(1, int(epochs) + 1):
+    averaged = optimizer.ema_weights if ema_eval else contextlib.nullcontext
+    for epoch in range(int(start_epoch) + 1, int(epochs) + 1):
         train_metrics = g["train_one_epoch"](model, train_loader, optimizer, device, loss_fn, fusion_mode,
                                              fusion_align_weight=fusion_align_weight, grad_sync=grad_sync)
-        val_metrics = g["evaluate"](model, val_loader, device, loss_fn, fusion_mode,
-                                    fusion_align_weight=fusion_align_weight, group=group)
-        if scheduler is not None:
-            scheduler.step()
-        history.append({"train": train_metrics, "val": val_metrics,
-                        "lr": [float(pg["lr"]) for pg in optimizer.param_groups]})
-        if val_metrics["f1"] > best_f1:
-            best_f1, best_epoch, stale = float(val_metrics["f1"]), epoch, 0
-            if checkpoint_path is not None and (not D.is_dist() or td.get_rank() == 0):
-                g["save_checkpoint"](model, checkpoint_path, best_f1, config)
-        else:
+        with averaged():  # one swap in, one out: the evaluation and the checkpoint both see the averaged weights
+            val_metrics = g["evaluate"](model, val_loader, device, loss_fn, fusion_mode,
+                                        fusion_align_weight=fusion_align_weight, group=group)
+            if scheduler is not None:
+                scheduler.step()
+            history.append({"train": train_metrics, "val": val_metrics,
+                            "lr": [float(pg["lr"]) for pg in optimizer.param_groups]})
+            improved = val_metrics["f1"] > best_f1
+            if improved:
+                best_f1, best_epoch, stale = float(val_metrics["f1"]), epoch, 0
+                if checkpoint_path is not None and (not D.is_dist() or td.get_rank() == 0):
+                    if save_optimizer:
+                        g["save_checkpoint"](model, checkpoint_path, best_f1, config, optimizer=optimizer, epoch=epoch)
+                    else:
+                        g["save_checkpoint"](model, checkpoint_path, best_f1, config)
+        if not improved:
             stale += 1
             if early_stopping_patience > 0 and stale >= early_stopping_patience:
                 stopped = True
@@ -414,9 +440,29 @@ def fit(model: nn.Module, train_loader, val_loader, optimizer, device, loss_fn: 
             "history": history}
 
 
-def save_checkpoint(model: nn.Module, path, val_f1: float, config: Optional[dict] = None) -> None:
+def save_checkpoint(model: nn.Module, path, val_f1: float, config: Optional[dict] = None, optimizer=None,
+                    epoch: Optional[int] = None) -> None:
     """train.py:1141-1144 checkpoint format {"model", "val_f1", "config"} (state-dict keys identical to the
     reference's, so ``optimized_runtime.TorchModelRunner`` and the reference's loaders read it).  Tensors are
-    moved to the host; after FusedAdam re-homing they are views of its flat buffers, so they are copied out."""
+    moved to the host; after FusedAdam re-homing they are views of its flat buffers, so they are copied out.
+    ``optimizer`` given: the file also carries ``"optimizer"`` (its ``state_dict()``), ``"epoch"`` and ``"best_f1"``
+    for ``load_training_state``; the three keys above are unchanged."""
     state = {k: v.detach().to("cpu", copy=True) for k, v in model.state_dict().items()}
-    torch.save({"model": state, "val_f1": float(val_f1), "config": dict(config or {})}, str(path))
+    ckpt = {"model": state, "val_f1": float(val_f1), "config": dict(config or {})}
+    if optimizer is not None:
+        ckpt.update(optimizer=optimizer.state_dict(), epoch=int(epoch or 0), best_f1=float(val_f1))
+    torch.save(ckpt, str(path))
+
+
+def load_training_state(path, model: nn.Module, optimizer) -> Dict[str, float]:
+    """Resume from a checkpoint written with ``save_checkpoint(..., optimizer=...)`` (``fit(save_optimizer=True)``):
+    the model's state dict first (in place: re-homed parameters stay views of the optimizer's flat buffers), then the
+    optimizer's moments, step counts and EMA.  A checkpoint written under ``ema_eval`` holds the AVERAGED weights as
+    ``"model"``; its optimizer state carries the live ones and puts them back.  Returns ``{"epoch", "best_f1"}`` for
+    ``fit(start_epoch=..., best_f1=...)``."""
+    ckpt = torch.load(str(path), map_location="cpu", weights_only=True)
+    if "optimizer" not in ckpt:
+        raise KeyError(f"{path} holds no optimizer state (written without save_optimizer)")
+    model.load_state_dict(ckpt["model"])
+    optimizer.load_state_dict(ckpt["optimizer"])
+    return {"epoch": int(ckpt.get("epoch", 0)), "best_f1": float(ckpt.get("best_f1", ckpt.get("val_f1", -1.0)))}
