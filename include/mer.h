@@ -504,11 +504,27 @@ int mer_partials_sum2(int C, int parts, float* in, float* out, float* in2, float
 
 /* dw[k][c][r][s] += sum_p dy[p][k] x(p; r,s,c) for c < Creal, fp32 PyTorch layout (dw initialised).  The
  * pixel reduction is split `splits` ways; each split writes an fp32 slab [K][R*S*C] into `workspace`
- * (splits*K*R*S*C floats), then a reduce pass sums the slabs into dw (deterministic, no atomics). */
+ * (splits*K*R*S*C floats), then a reduce pass sums the slabs into dw (deterministic, no atomics).
+ * One plan (mer_conv_wgrad_plan) is the single description of a weight-gradient launch: which kernel runs, how many
+ * splits it is asked for, how many slabs it then writes and how large the workspace is.  Every entry point below
+ * launches from that plan, so a caller that plans first and passes on the plan's variant and splits gets exactly the
+ * slabs the plan named. */
 int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad, const void* x,
                    const void* dy, float* dw, int splits, float* workspace, void* stream);
-/* mer_conv_wgrad with an explicit kernel: -1 auto, 1 4-wave tiles, 2 8-wave tiles, 3 with a 2-deep register prefetch,
- * 4-7 the global_load_lds rings, 8 two K-groups per workgroup.  1-7 give the same bits; 8 agrees to fp32 rounding.
+/* The plan of the weight-gradient launch with these arguments; host-only (no HIP call, no GPU needed).
+ * out = {resolved variant, splits to pass to the launch, slabs the launch writes, workspace floats}.
+ * variant -1: 8 (two K-groups) where K > 64, stride == 1 and R*S > 1, else 4; never the strip kernel.  splits <= 0:
+ * the library chooses (the rings: ~768 workgroups and a least pixel count per split; the strip: one workgroup per CU).
+ * The slabs are <= splits: a split is a whole number of 64-pixel granules (the strip kernel: of image rows) and none is
+ * empty; the workspace is sized by the splits (splits * K * R*S*C floats), the fold reads the slabs.  Planning again
+ * from the resolved (variant, splits) returns the same record.  hipErrorInvalidValue, with out untouched, for what the
+ * launch refuses: C % 8, K % 8, an empty tensor, R*S > 49, a variant outside -1..10, and for 9 / 10 the strip kernel's
+ * conditions (see mer_conv_wgrad_ex). */
+int mer_conv_wgrad_plan(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad, int variant,
+                        int splits, long long* out);
+/* mer_conv_wgrad with an explicit kernel: -1 the plan's choice, 1 4-wave tiles, 2 8-wave tiles, 3 with a 2-deep
+ * register prefetch, 4-7 the global_load_lds rings, 8 two K-groups per workgroup.  1-7 give the same bits; 8 agrees to
+ * fp32 rounding.  splits <= 0: the plan's choice (the workspace must then hold mer_conv_wgrad_plan's floats).
  * 9 / 10: the strip kernel for 3x3 / stride-1 / pad-1 convs -- all nine taps of a (64 / 32 output channels) x (64
  * input channels) tile from one LDS strip of X rows, the reduction over a padded pixel index (rows of W + 1 slots, one
  * pad row per image).  Its splits are ranges of image rows: N * (H + 1) rows in ceil(rows / splits)-row pieces, every
@@ -517,11 +533,13 @@ int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, int S, i
  * 3, stride = pad = 1, C % 64 == 0, K % 64 (9) or K % 32 (10) == 0, Creal == C and W <= 126; -1 never picks it. */
 int mer_conv_wgrad_ex(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad, const void* x,
                       const void* dy, float* dw, int splits, float* workspace, int variant, void* stream);
-/* The split-K pass of mer_conv_wgrad alone: workspace = splits x [K][R*S*C] fp32 partial slabs, folded later by
- * mer_wgrad_fold_batch (one launch for all weight gradients of a backward segment). */
+/* The split-K pass of mer_conv_wgrad alone: workspace = splits x [K][R*S*C] fp32 partial slabs, of which the launch
+ * writes the first mer_conv_wgrad_plan slabs; mer_wgrad_fold_batch folds them later (one launch for all weight
+ * gradients of a backward segment). */
 int mer_conv_wgrad_partials(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
                             const void* dy, int splits, float* workspace, int variant, void* stream);
-/* Fold n <= 32 deferred slab sets in one launch.  rows: n x 8 int64 {ws, dw, map, K, C, Creal, R*S, splits}:
+/* Fold n <= 32 deferred slab sets in one launch.  rows: n x 8 int64 {ws, dw, map, K, C, Creal, R*S, splits}, `splits`
+ * being the slabs the launch wrote (mer_conv_wgrad_plan's out[2], not the splits it was asked for):
  * dw[k][c][r][s] += sum_z ws[z][k][(r*S+s)*C + c] for c < Creal (fixed split order), or, with map != NULL
  * (int32 [R*S*C], -1 = dropped), dw[k][map[j]] += sum_z ws[z][k][j] with Creal = dw floats per k. */
 int mer_wgrad_fold_batch(int n, const long long* rows, void* stream);

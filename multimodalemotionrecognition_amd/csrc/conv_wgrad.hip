@@ -469,23 +469,6 @@ __global__ __launch_bounds__(64 * WM * WN * KG, KG > 1 ? WM * WN * KG / 4 : 2) v
   CTP(4);
 }
 
-template <int BM_, int BN_, int WM, int WN, int STAGES, int KS = 64, int KG = 1>
-int launch_wgrad_pipe(const WgradGeom& g0, dim3 grid, hipStream_t st) {
-  const size_t ring = (size_t)KG * STAGES * KS * (BM_ + BN_) * sizeof(bf16_t);
-  const size_t xchg = (size_t)(KG - 1) * BM_ * (BN_ + 4) * sizeof(float);
-  const size_t lds = ring > xchg ? ring : xchg;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pipe_kernel<BM_, BN_, WM, WN, STAGES, KS, KG>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return (int)hipErrorInvalidConfiguration;
-  // split-major 1-D grid over xcd_tile's XCD chunks: the tiles of one split (same dY rows, same shifted X windows)
-  // share an L2 (DESIGN.md section 4e'': layer1 / stem wgrad fetch 244 -> 67 MB per launch)
-  WgradGeom g = g0;
-  g.flat = 1;
-  const dim3 gr(grid.x * grid.z, 1, 1);
-  hipLaunchKernelGGL((wgrad_pipe_kernel<BM_, BN_, WM, WN, STAGES, KS, KG>), gr, dim3(64 * WM * WN * KG), lds, st, g);
-  return (int)hipSuccess;
-}
-
 // ---------------------------------------------------------------------------------------
 // Strip weight gradient of a 3x3 / stride-1 / pad-1 conv (variants 9 and 10): all nine taps from ONE LDS strip.
 // wgrad_pipe_kernel tiles the (tap, c) axis over workgroups, so every 64x128 tile DMAs its own dY tile and its own
@@ -730,34 +713,6 @@ __global__ __launch_bounds__(768, 3) void wgrad_strip_kernel(StripGeom g) {
       for (int rr = 0; rr < 4; ++rr) slab[(long)(k0 + i * 16 + g4 * 4 + rr) * Ntot + nn] = acc[s][i][rr];
     }
   CTP(4);
-}
-
-// launches the strip kernel over `splits` row ranges (in: requested, out: the count used -- every split non-empty);
-// hipErrorInvalidValue where the X ring would not fit (W > 126) or the padded index leaves 31 bits
-template <int KB>
-int launch_wgrad_strip(const WgradGeom& g0, int& splits, hipStream_t st) {
-  constexpr int STAGES = 4;
-  StripGeom g{};
-  g.N = g0.N; g.H = g0.H; g.W = g0.W; g.C = g0.C; g.K = g0.K;
-  g.X = g0.X; g.dY = g0.dY; g.ws = g0.ws; g.ldy = (int)g0.ldy;
-  const int Wp = g.W + 1, Hp = g.H + 1;
-  const long TR = (long)g.N * Hp;
-  if (g0.ldy >= (1 << 24) || (TR + Hp) * Wp >= (1L << 30)) return (int)hipErrorInvalidValue;
-  const int chunks = (2 * (Wp + 1) + 63) / 64 + STAGES;
-  int xc = 1;
-  while (xc < chunks) xc *= 2;
-  if (xc > 8) return (int)hipErrorInvalidValue;
-  g.xrows = xc * 64;
-  if (splits < 1) splits = 1;
-  g.rows_per_split = (int)((TR + splits - 1) / splits);
-  splits = (int)((TR + g.rows_per_split - 1) / g.rows_per_split);
-  const size_t lds = ((size_t)g.xrows * 64 + (size_t)STAGES * 64 * KB) * sizeof(bf16_t);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_strip_kernel<KB, STAGES>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return (int)hipErrorInvalidValue;
-  const int tiles = (g.C / 64) * (g.K / KB);
-  hipLaunchKernelGGL((wgrad_strip_kernel<KB, STAGES>), dim3(splits * tiles), dim3(768), lds, st, g);
-  return (int)hipSuccess;
 }
 
 // slab0[i] = sum_z ws[z][i] over the flat [K][R*S*C] index.  A block owns E = 256/SG consecutive elements
@@ -1068,6 +1023,209 @@ __global__ __launch_bounds__(256) void wgrad_fold_batch_kernel(FoldTable t) {
   else fold_tiled<kFoldSlots>(R, v - R.blk0, lds);
 }
 
+// ---------------------------------------------------------------------------------------
+// The weight-gradient plan.  Which kernel a weight gradient runs, how many splits it is asked for, how many slabs it
+// then writes (every split non-empty, so fewer than asked where the rounding says so), the grid, the LDS bytes and the
+// workspace are resolved ONCE, by wgrad_plan() below, from the geometry and the requested variant and splits.  The
+// entry points launch from the plan and mer_conv_wgrad_plan reports from it: the caller sizes its workspace and tells
+// the deferred fold (mer_wgrad_fold_batch) its slab count from the same record the launch runs by, so the fold cannot
+// sum slabs nobody wrote or drop written ones.
+// ---------------------------------------------------------------------------------------
+enum WgradForm { kWgradReg, kWgradRing, kWgradStrip };  // wgrad_kernel / wgrad_pipe_kernel / wgrad_strip_kernel
+
+// a variant's kernel as a type; the register-staged and ring tiles are BM x 128 (output channels x (tap, c) columns)
+template <int BM_, int WM_, int WN_, int PF_>
+struct RegTile {
+  static constexpr WgradForm form = kWgradReg;
+  static constexpr int BM = BM_, WM = WM_, WN = WN_, PF = PF_, STAGES = 0, KS = 64, KG = 1;
+};
+template <int BM_, int STAGES_, int KS_ = 64, int KG_ = 1>
+struct RingTile {
+  static constexpr WgradForm form = kWgradRing;
+  static constexpr int BM = BM_, WM = 2, WN = 4, STAGES = STAGES_, KS = KS_, KG = KG_;
+};
+template <int KB>
+struct StripTile {  // BM: the tile's output channels
+  static constexpr WgradForm form = kWgradStrip;
+  static constexpr int BM = KB, WM = 3, WN = 4, STAGES = 4, KS = 64, KG = 1;
+};
+
+struct WgradPlan {
+  int err;        // what the launch returns instead of launching (hipSuccess: launch)
+  int variant;    // the resolved variant (never -1)
+  int splits;     // the splits the launch is asked for (resolved: never <= 0); the workspace holds this many slabs
+  int slabs;      // the slabs the launch writes (<= splits): every split non-empty
+  int per_split;  // output pixels (a multiple of 64) or, strip, image rows (each image's pad row counted) per slab
+  WgradForm form;
+  int BM, STAGES, KS, KG;  // tile height (64 / 128; strip: its output channels), ring depth, K-step, K-groups
+  int xrows;               // strip: rows of the X ring
+  unsigned grid_x, grid_z, threads;
+  size_t lds;              // dynamic LDS bytes
+  long long ws_floats;     // splits x K x R*S*C
+};
+
+// The kernel of a resolved variant: calls f(tile type{}) and returns what f returns.  The one copy of the ladder:
+// wgrad_plan() records the tile through it, launch_wgrad_plan() instantiates the kernel through it.
+template <int BM, class F>
+int wgrad_tile_bm(int variant, F&& f) {
+  switch (variant) {
+    case 1: return f(RegTile<BM, 2, 2, 1>{});
+    case 3: return f(RegTile<BM, 2, 4, 2>{});
+    case 4: return f(RingTile<BM, 2>{});
+    case 5: return f(RingTile<BM, 3>{});
+    case 8: return f(RingTile<BM, 2, 64, 2>{});
+    case 9: return f(StripTile<64>{});
+    case 10: return f(StripTile<32>{});
+  }
+  if constexpr (BM == 128) {  // the 32-pixel K-steps are built for the 128-row tile only
+    if (variant == 6) return f(RingTile<128, 4, 32>{});
+    if (variant == 7) return f(RingTile<128, 3, 32>{});
+  } else {
+    if (variant == 6) return f(RingTile<64, 3>{});
+  }
+  return f(RegTile<BM, 2, 4, 1>{});
+}
+template <class F>
+int wgrad_tile(const WgradGeom& g, int variant, F&& f) {
+  return g.K <= 64 ? wgrad_tile_bm<64>(variant, f) : wgrad_tile_bm<128>(variant, f);
+}
+
+// `variant`, `splits`: as the entry points take them (-1 / <= 0: choose).
+WgradPlan wgrad_plan(const WgradGeom& g, int variant, int splits) {
+  WgradPlan p{};
+  p.err = (int)hipErrorInvalidValue;
+  if (g.N < 1 || g.H < 1 || g.W < 1 || g.C < 1 || g.K < 1 || g.R < 1 || g.S < 1 || g.st < 1 || g.pad < 0 ||
+      g.H + 2 * g.pad < g.R || g.W + 2 * g.pad < g.S)
+    return p;
+  if (g.C % 8 || g.K % 8 || variant < -1 || variant > 10 || g.R * g.S > 49) return p;
+  const long P = (long)g.N * g.Ho * g.Wo, Ntot = (long)g.R * g.S * g.C;
+  if (P >= (1L << 31)) return p;  // the kernels count pixels in 32 bits
+  // The default form for the stride-1 3x3 convs with K > 64 output channels (round 6): variant 8, two K-groups of 8
+  // waves per workgroup (in-workgroup split-K over the pixels).  A launch of it covers the pixels of two one-group
+  // splits: half the splits -- and half the fp32 slabs written and folded (~340 of the ~520 MB per step) -- for the
+  // same waves per CU, so it targets half the workgroups.  The others keep the one-group ring (4): the 64-channel stem
+  // / layer1 (its 48 KB blocks run three per CU, the 96 KB two-group block one: stem 78 -> 110 us standalone,
+  // profiles/r06/bench_wgrad_kg.txt), and the stride-2 / 1x1 wgrads, whose slabs are small and whose kernels ran
+  // 2-8 us slower each in the serialized trunk (profiles/r06/trunk_table_serial.txt).
+  // Never the strip kernel: it sums in another fp32 order than the rings, and over the benchmark's 60 Adam steps that
+  // rounding grows into parameter differences far beyond rounding (an element whose gradient is at rounding level
+  // moves +lr or -lr), so the trunk keeps the rings' bits.
+  if (variant == -1) variant = (g.K > 64 && g.st == 1 && g.R * g.S > 1) ? 8 : 4;
+  p.variant = variant;
+  wgrad_tile(g, variant, [&](auto t) {
+    using T = decltype(t);
+    p.form = T::form;
+    p.BM = T::BM; p.STAGES = T::STAGES; p.KS = T::KS; p.KG = T::KG;
+    p.threads = 64 * T::WM * T::WN * T::KG;
+    return 0;
+  });
+  if (p.form == kWgradStrip) {
+    // 3x3 / stride-1 / pad-1 convs on whole 64-channel chunks and whole tiles of output channels only; a dY row
+    // stride, a padded pixel index and an X ring (a power of two of 64-row chunks >= 2 (W + 2) rows + the dY ring's
+    // depth: W <= 126) the kernel's address arithmetic holds
+    if (g.R != 3 || g.S != 3 || g.st != 1 || g.pad != 1 || g.C % 64 || g.K % p.BM || g.Creal != g.C) return p;
+    const int Wp = g.W + 1, Hp = g.H + 1;
+    const long TR = (long)g.N * Hp;  // image rows, each image's pad row counted
+    if (g.ldy >= (1 << 24) || (TR + Hp) * Wp >= (1L << 30)) return p;
+    int xc = 1;
+    while (xc < (2 * (Wp + 1) + 63) / 64 + p.STAGES) xc *= 2;
+    if (xc > 8) return p;
+    p.xrows = xc * 64;
+    // A tile spans every tap, so a split is (C / 64) * (K / tile) workgroups: one 12-wave workgroup per CU (256), and
+    // at least 1024 padded pixels per split.
+    const long stiles = (g.C / 64) * (g.K / p.BM);
+    if (splits <= 0) splits = (int)std::max(1L, std::min(256 / stiles, TR * Wp / 1024));
+    p.per_split = (int)((TR + splits - 1) / splits);
+    p.slabs = (int)((TR + p.per_split - 1) / p.per_split);
+    p.grid_x = (unsigned)(p.slabs * stiles);
+    p.grid_z = 1;
+    p.lds = ((size_t)p.xrows * 64 + (size_t)p.STAGES * 64 * p.BM) * sizeof(bf16_t);
+  } else {
+    const long tiles = ((g.K + p.BM - 1) / p.BM) * ((Ntot + 127) / 128);
+    if (splits <= 0) {
+      // Target workgroups per launch: 768, 8 waves each, 3 per CU (256 / 384 / 512 lose 3.1 / 1.3 / 0.3 % of the
+      // step, 1024 loses 0.4 %).  Pixels per split, at least (tools/bench_conv.py on the ResNet18 layers, MI355X):
+      // 1024 in general -- more, shorter splits lose to the fold of their partial slabs -- but 256 for the tiny 1x1
+      // downsample outputs (a K loop of 16 64-pixel steps per split was the whole time: 26 -> 19 us) and 512 where the
+      // output has so many tiles that 1024 leaves only 4 splits (layer4 3x3: 65 -> 58 us).  A two-K-group workgroup
+      // counts as two.
+      const long kg = variant == 8 ? 2 : 1;
+      const long min_pix = Ntot * g.K <= 65536 ? 256 : (tiles >= 96 ? 512 : 1024);
+      splits = (int)std::max(1L, std::min((768 + kg * tiles - 1) / (kg * tiles), P / (kg * min_pix)));
+    }
+    p.per_split = (int)(((P + splits - 1) / splits + 63) / 64 * 64);
+    p.slabs = (int)((P + p.per_split - 1) / p.per_split);
+    // the rings: a split-major 1-D grid over xcd_tile's XCD chunks -- the tiles of one split (same dY rows, same
+    // shifted X windows) share an L2 (DESIGN.md section 4e'': layer1 / stem wgrad fetch 244 -> 67 MB per launch);
+    // the register-staged kernels: splits on grid z
+    p.grid_x = (unsigned)(p.form == kWgradRing ? tiles * p.slabs : tiles);
+    p.grid_z = p.form == kWgradRing ? 1 : (unsigned)p.slabs;
+    if (p.form == kWgradRing) {
+      const size_t ring = (size_t)p.KG * p.STAGES * p.KS * (p.BM + 128) * sizeof(bf16_t);
+      const size_t xchg = (size_t)(p.KG - 1) * p.BM * (128 + 4) * sizeof(float);  // the K-groups' tile exchange
+      p.lds = ring > xchg ? ring : xchg;
+    }
+  }
+  p.splits = splits;
+  p.ws_floats = (long long)splits * g.K * Ntot;
+  p.err = (int)hipSuccess;
+  return p;
+}
+
+template <class T>
+int launch_wgrad_tile(const WgradGeom& g0, const WgradPlan& p, hipStream_t st) {
+  // the tile this walk of the ladder arrived at is the one the plan sized the grid and the LDS for
+  if (T::form != p.form || T::BM != p.BM || T::STAGES != p.STAGES || T::KS != p.KS || T::KG != p.KG)
+    return (int)hipErrorInvalidConfiguration;
+  const dim3 grid(p.grid_x, 1, p.grid_z);
+  if constexpr (T::form == kWgradStrip) {
+    StripGeom g{};
+    g.N = g0.N; g.H = g0.H; g.W = g0.W; g.C = g0.C; g.K = g0.K;
+    g.X = g0.X; g.dY = g0.dY; g.ws = g0.ws; g.ldy = (int)g0.ldy;
+    g.xrows = p.xrows;
+    g.rows_per_split = p.per_split;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_strip_kernel<T::BM, T::STAGES>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess)
+      return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((wgrad_strip_kernel<T::BM, T::STAGES>), grid, dim3(p.threads), p.lds, st, g);
+  } else {
+    WgradGeom g = g0;
+    g.pix_per_split = p.per_split;
+    if constexpr (T::form == kWgradRing) {
+      g.flat = 1;
+      if (hipFuncSetAttribute(
+              reinterpret_cast<const void*>(&wgrad_pipe_kernel<T::BM, 128, T::WM, T::WN, T::STAGES, T::KS, T::KG>),
+              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess)
+        return (int)hipErrorInvalidConfiguration;
+      hipLaunchKernelGGL((wgrad_pipe_kernel<T::BM, 128, T::WM, T::WN, T::STAGES, T::KS, T::KG>), grid,
+                         dim3(p.threads), p.lds, st, g);
+    } else {
+      hipLaunchKernelGGL((wgrad_kernel<T::BM, 128, T::WM, T::WN, T::PF>), grid, dim3(p.threads), 0, st, g);
+    }
+  }
+  return (int)hipSuccess;
+}
+
+// the only place that instantiates and launches the weight-gradient kernels
+int launch_wgrad_plan(const WgradGeom& g, const WgradPlan& p, hipStream_t st) {
+  if (p.err != (int)hipSuccess) return p.err;
+  return wgrad_tile(g, p.variant, [&](auto t) { return launch_wgrad_tile<decltype(t)>(g, p, st); });
+}
+
+WgradGeom wgrad_geom(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad, const void* x,
+                     const void* dy, long ldy, float* workspace) {
+  WgradGeom g{};
+  g.N = N; g.H = H; g.W = W; g.C = C; g.Creal = Creal; g.K = K;
+  g.R = R; g.S = S; g.st = stride; g.pad = pad;
+  if (stride > 0) {
+    g.Ho = (H + 2 * pad - R) / stride + 1;
+    g.Wo = (W + 2 * pad - S) / stride + 1;
+  }
+  g.X = (const bf16_t*)x; g.dY = (const bf16_t*)dy; g.ws = workspace;
+  g.ldy = ldy > 0 ? ldy : K;
+  return g;
+}
+
 }  // namespace
 
 MER_API int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
@@ -1078,79 +1236,35 @@ MER_API int mer_conv_wgrad(int N, int H, int W, int C, int Creal, int K, int R, 
 static int conv_wgrad_impl(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
                            const void* x, const void* dy, long ldy, float* dw, int splits, float* workspace,
                            int variant, void* stream, bool fold = true) {
-  if (C % 8 || K % 8 || variant < -1 || variant > 10 || R * S > 49) return (int)hipErrorInvalidValue;
-  if (variant == -1) variant = 4;
-  // the strip kernel (9: 64 output channels per tile, 10: 32) takes 3x3 / stride-1 / pad-1 convs on whole 64-channel
-  // chunks only
-  const bool strip = variant == 9 || variant == 10;
-  if (strip && (R != 3 || S != 3 || stride != 1 || pad != 1 || C % 64 || K % (variant == 9 ? 64 : 32) || Creal != C))
-    return (int)hipErrorInvalidValue;
-  WgradGeom g{};
-  g.N = N; g.H = H; g.W = W; g.C = C; g.Creal = Creal;
-  g.Ho = (H + 2 * pad - R) / stride + 1; g.Wo = (W + 2 * pad - S) / stride + 1; g.K = K;
-  g.R = R; g.S = S; g.st = stride; g.pad = pad;
-  g.X = (const bf16_t*)x; g.dY = (const bf16_t*)dy; g.ws = workspace;
-  g.ldy = ldy > 0 ? ldy : K;
-  const int P = N * g.Ho * g.Wo;
-  const int splits_req = splits;
-  if (splits < 1) splits = 1;
-  g.pix_per_split = ((P + splits - 1) / splits + 63) / 64 * 64;
-  splits = (P + g.pix_per_split - 1) / g.pix_per_split;  // every split non-empty (<= requested)
-  const int Ntot = R * S * C;
+  const WgradGeom g = wgrad_geom(N, H, W, C, Creal, K, R, S, stride, pad, x, dy, ldy, workspace);
+  const WgradPlan p = wgrad_plan(g, variant, splits);
   hipStream_t st = (hipStream_t)stream;
-  int rc = (int)hipSuccess;  // of a launcher that can refuse (LDS size, geometry): nothing is folded then
-  if (strip) {  // splits are ranges of image rows there: `splits` becomes the count it used
-    splits = splits_req;
-    rc = variant == 9 ? launch_wgrad_strip<64>(g, splits, st) : launch_wgrad_strip<32>(g, splits, st);
-  } else if (K <= 64) {
-    dim3 grid(((Ntot + 127) / 128) * ((K + 63) / 64), 1, splits);
-    if (variant == 1)
-      hipLaunchKernelGGL((wgrad_kernel<64, 128>), grid, dim3(256), 0, st, g);
-    else if (variant == 4)
-      rc = launch_wgrad_pipe<64, 128, 2, 4, 2>(g, grid, st);
-    else if (variant == 8)
-      rc = launch_wgrad_pipe<64, 128, 2, 4, 2, 64, 2>(g, grid, st);
-    else if (variant == 5 || variant == 6)
-      rc = launch_wgrad_pipe<64, 128, 2, 4, 3>(g, grid, st);
-    else if (variant == 3)
-      hipLaunchKernelGGL((wgrad_kernel<64, 128, 2, 4, 2>), grid, dim3(512), 0, st, g);
-    else
-      hipLaunchKernelGGL((wgrad_kernel<64, 128, 2, 4>), grid, dim3(512), 0, st, g);
-  } else {
-    dim3 grid(((Ntot + 127) / 128) * ((K + 127) / 128), 1, splits);
-    if (variant == 1)
-      hipLaunchKernelGGL((wgrad_kernel<128, 128>), grid, dim3(256), 0, st, g);
-    else if (variant == 4)
-      rc = launch_wgrad_pipe<128, 128, 2, 4, 2>(g, grid, st);
-    else if (variant == 8)
-      rc = launch_wgrad_pipe<128, 128, 2, 4, 2, 64, 2>(g, grid, st);
-    else if (variant == 5)
-      rc = launch_wgrad_pipe<128, 128, 2, 4, 3>(g, grid, st);
-    else if (variant == 6)
-      rc = launch_wgrad_pipe<128, 128, 2, 4, 4, 32>(g, grid, st);
-    else if (variant == 7)
-      rc = launch_wgrad_pipe<128, 128, 2, 4, 3, 32>(g, grid, st);
-    else if (variant == 3)
-      hipLaunchKernelGGL((wgrad_kernel<128, 128, 2, 4, 2>), grid, dim3(512), 0, st, g);
-    else
-      hipLaunchKernelGGL((wgrad_kernel<128, 128, 2, 4>), grid, dim3(512), 0, st, g);
-  }
+  const int rc = launch_wgrad_plan(g, p, st);  // a refused plan or launch (LDS size): nothing is folded then
   if (rc != (int)hipSuccess) return rc;
   if (!fold) MER_LAUNCH_CHECK();  // partial slabs left for mer_wgrad_fold_batch
   constexpr int fold_max = 16;  // most slabs folded in the single fold+scatter pass
-  if (splits > fold_max) {  // many partial slabs: a wide reduce first (one serial chain per element was latency-bound)
-    const int SG = splits >= 64 ? 16 : 8;
+  if (p.slabs > fold_max) {  // many partial slabs: a wide reduce first (one serial chain per element was latency-bound)
+    const int SG = p.slabs >= 64 ? 16 : 8;
     const long total = (long)K * R * S * C;
     const int E = 256 / SG;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + E - 1) / E)), dim3(256), 0, st, K, C, Creal, R * S,
-                       splits, SG, workspace);
+                       p.slabs, SG, workspace);
     hipLaunchKernelGGL(wgrad_scatter_kernel, dim3((Creal + 31) / 32, K), dim3(256), 0, st, C, Creal, R * S, workspace,
                        dw);
   } else {  // few slabs: fold and scatter in one pass
     hipLaunchKernelGGL(wgrad_fold_scatter_kernel, dim3((Creal + 31) / 32, K), dim3(256), 0, st, K, C, Creal, R * S,
-                       splits, workspace, dw);
+                       p.slabs, workspace, dw);
   }
   MER_LAUNCH_CHECK();
+}
+
+MER_API int mer_conv_wgrad_plan(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,
+                                int variant, int splits, long long* out) {
+  const WgradPlan p = wgrad_plan(wgrad_geom(N, H, W, C, Creal, K, R, S, stride, pad, nullptr, nullptr, K, nullptr),
+                                 variant, splits);
+  if (p.err != (int)hipSuccess) return p.err;
+  out[0] = p.variant; out[1] = p.splits; out[2] = p.slabs; out[3] = p.ws_floats;
+  return (int)hipSuccess;
 }
 
 MER_API int mer_conv_wgrad_ex(int N, int H, int W, int C, int Creal, int K, int R, int S, int stride, int pad,

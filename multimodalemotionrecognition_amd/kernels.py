@@ -7,6 +7,8 @@ exception), then pass raw pointers and the current stream.
 """
 from __future__ import annotations
 
+import collections
+import ctypes
 import os
 
 import torch
@@ -648,47 +650,24 @@ def partials_sum(parts_buf, out, rows=None):
     return out
 
 
-# Pixels per wgrad split, at least (tools/bench_conv.py on the ResNet18 layers, MI355X): 1024 in general -- more,
-# shorter splits lose to the fold of their partial slabs -- but 256 for the tiny 1x1 downsample outputs (a K loop of
-# 16 64-pixel steps per split was the whole time: 26 -> 19 us) and 512 where the output has so many tiles that
-# 1024 leaves only 4 splits (layer4 3x3: 65 -> 58 us).
-# Target workgroups per wgrad launch: 768 (256 / 384 / 512 lose 3.1 / 1.3 / 0.3 % of the step, 1024 loses 0.4 %).
-_WGRAD_WGS = 768
-# The trunk's default wgrad form for the stride-1 3x3 convs with K > 64 output channels (round 6): conv_wgrad.hip variant 8,
-# two K-groups of 8 waves per workgroup (in-workgroup split-K over the pixels).  A launch of it covers the pixels of two
-# one-group splits: half the splits -- and half the fp32 slabs written and folded (~340 of the ~520 MB per step) -- for
-# the same waves per CU, so it targets _WGRAD_WGS / 2 workgroups.  The others keep the one-group ring (4): the
-# 64-channel stem / layer1 (its 48 KB blocks run three per CU, the 96 KB two-group block one: stem 78 -> 110 us
-# standalone, profiles/r06/bench_wgrad_kg.txt), and the stride-2 / 1x1 wgrads, whose slabs are small and whose kernels
-# ran 2-8 us slower each in the serialized trunk (profiles/r06/trunk_table_serial.txt).
-WGRAD_VARIANT = 8
-# conv_wgrad.hip's strip kernel (explicit variants 9 / 10 only): all nine taps of a 3x3 / stride-1 / pad-1 conv from one LDS
-# strip of X rows.  A tile spans every tap, so a split is (C / 64) * (K / tile) workgroups; it targets one 12-wave
-# workgroup per CU.  The automatic choice does not pick it: it sums in another fp32 order than the rings, and over the
-# benchmark's 60 Adam steps that rounding grows into parameter differences far beyond rounding (an element whose
-# gradient is at rounding level moves +lr or -lr), so the trunk keeps the rings' bits.
-_WGRAD_STRIP_KB = {9: 64, 10: 32}  # output channels per tile
-_WGRAD_STRIP_WGS = 256
+WgradPlan = collections.namedtuple("WgradPlan", "variant splits slabs ws_floats")
+_WGRAD_PLANS = {}
 
 
-def wgrad_strip_split_count(N: int, H: int, splits: int) -> int:
-    """The split count a strip wgrad launch (variants 9, 10) asked for ``splits`` really uses (conv_wgrad.hip
-    launch_wgrad_strip): whole image rows per split, each image's pad row counted, every split non-empty."""
-    rows = N * (H + 1)
-    per = -(-rows // max(1, int(splits)))
-    return -(-rows // per)
-
-
-def _wgrad_min_pix(out_elems, tiles):
-    return 256 if out_elems <= 65536 else (512 if tiles >= 96 else 1024)
-
-
-def wgrad_split_count(P: int, splits: int) -> int:
-    """The split count a wgrad launch asked for ``splits`` over P output pixels really uses (conv_wgrad.hip
-    conv_wgrad_impl): 64-pixel granules per split, every split non-empty."""
-    splits = max(1, int(splits))
-    pps = (-(-P // splits) + 63) // 64 * 64
-    return -(-P // pps)
+def wgrad_plan(N, H, W, C, creal, Kc, R, S, stride, pad, variant=-1, splits=None):
+    """mer_conv_wgrad_plan: the single description of a weight-gradient launch (conv_wgrad.hip wgrad_plan) -- the
+    resolved variant, the splits to pass to the launch, the slabs it writes (what the fold is told) and the workspace
+    floats.  ``variant`` -1 / ``splits`` None: the library chooses.  Host-only and cached on its arguments; planning
+    again from a plan's (variant, splits) returns the same plan.  Raises on a geometry the launch refuses."""
+    key = tuple(int(a) for a in (N, H, W, C, creal, Kc, R, S, stride, pad, variant, splits or 0))
+    p = _WGRAD_PLANS.get(key)
+    if p is None:
+        out = (ctypes.c_longlong * 4)()
+        rc = LIB.call_int("mer_conv_wgrad_plan", *key, out)
+        if rc != 0:
+            raise MerKernelError(f"mer_conv_wgrad_plan{key} failed: {rc}")
+        p = _WGRAD_PLANS[key] = WgradPlan(*(int(v) for v in out))
+    return p
 
 
 class WgradFolds:
@@ -730,30 +709,16 @@ def conv_wgrad(x, dy, dw, R, S, stride, pad, creal=None, variant=-1, splits=None
         raise ValueError("conv_wgrad shapes")
     if tuple(dy.shape) != (N, Ho, Wo, Kc):
         raise ValueError("conv_wgrad shapes")
-    P = N * Ho * Wo
-    tiles = ((Kc + 127) // 128) * ((R * S * C + 127) // 128)
-    if variant == -1:  # (never the strip kernel: see above)
-        variant = WGRAD_VARIANT if (Kc > 64 and stride == 1 and R * S > 1) else 4
-    strip = variant in _WGRAD_STRIP_KB
-    kg = 2 if variant == 8 else 1  # K-groups per workgroup
-    if strip:
-        if splits is None:  # one workgroup per CU, >= 1024 padded pixels each
-            stiles = max(1, (C // 64) * (Kc // _WGRAD_STRIP_KB[variant]))
-            splits = max(1, min(_WGRAD_STRIP_WGS // stiles, N * (H + 1) * (W + 1) // 1024))
-        eff = wgrad_strip_split_count(N, H, splits)
-    else:
-        if splits is None:  # ~768 groups of 8 waves (3 per CU), >= _wgrad_min_pix pixels each
-            splits = int(max(1, min(-(-_WGRAD_WGS // (kg * tiles)),
-                                    P // (kg * _wgrad_min_pix(Kc * R * S * C, tiles)))))
-        eff = wgrad_split_count(P, splits)
-    ws = torch.empty(splits * Kc * R * S * C, device=x.device, dtype=torch.float32)
+    # (the deferred launch has no Creal: its plan is that of the padded channel count)
+    plan = wgrad_plan(N, H, W, C, C if defer is not None else creal, Kc, R, S, stride, pad, variant, splits)
+    ws = torch.empty(plan.ws_floats, device=x.device, dtype=torch.float32)
     if defer is not None:
         _launch("conv_wgrad", (N, H, W, C, Kc, R, stride), "mer_conv_wgrad_partials", N, H, W, C, Kc, R, S, stride,
-                pad, x.data_ptr(), dy.data_ptr(), int(splits), ws.data_ptr(), int(variant), stream_ptr())
-        defer.add(ws, dw, Kc, C, dw.numel() // Kc if dw_map is not None else creal, R * S, eff, dw_map)
+                pad, x.data_ptr(), dy.data_ptr(), plan.splits, ws.data_ptr(), plan.variant, stream_ptr())
+        defer.add(ws, dw, Kc, C, dw.numel() // Kc if dw_map is not None else creal, R * S, plan.slabs, dw_map)
         return
     _launch("conv_wgrad", (N, H, W, C, Kc, R, stride), "mer_conv_wgrad_ex", N, H, W, C, creal, Kc, R, S, stride, pad,
-            x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(splits), ws.data_ptr(), int(variant), stream_ptr())
+            x.data_ptr(), dy.data_ptr(), dw.data_ptr(), plan.splits, ws.data_ptr(), plan.variant, stream_ptr())
 
 
 def pack_input_s2d(x, y):

@@ -584,11 +584,8 @@ FUSED_DS_DGRAD = True
 class _WgradLane:
     """The weight-gradient launches of one backward (graph) segment and their deferred folds, flushed at join()."""
 
-    def __init__(self, device):
+    def __init__(self):
         self.folds = K.WgradFolds() if WGRAD_DEFER else None
-
-    def run(self, fn, *reads, block=None):
-        fn()
 
     def join(self):
         if self.folds is not None:
@@ -597,7 +594,7 @@ class _WgradLane:
 
 @torch.no_grad()
 def block_backward(trunk, blk: BasicBlock, sv, dx: torch.Tensor, grads, training: bool = True, pre=None,
-                   prev=None, arena=None, lane=None, bidx=None):
+                   prev=None, arena=None, lane=None):
     """Reverse of block_forward given dx = dL/d(block output); returns dL/d(block input).
 
     ``pre``: this block's bn2 / downsample-BN reductions already accumulated by the producer of ``dx``
@@ -610,7 +607,7 @@ def block_backward(trunk, blk: BasicBlock, sv, dx: torch.Tensor, grads, training
         arena = _StatsArena(trunk, dev, floats=_block_bwd_floats(sv))
     own_lane = lane is None
     if own_lane:
-        lane = _WgradLane(dev)
+        lane = _WgradLane()
     g_out = dx
     s = blk.stride
     C2 = bc2.shape[-1]
@@ -641,7 +638,7 @@ def block_backward(trunk, blk: BasicBlock, sv, dx: torch.Tensor, grads, training
     # conv2 (its dgrad also reduces bn1's backward sums: g = da1 * (ba1 > 0))
     w2 = _grad(blk.conv2.weight, grads)
     if w2 is not None:
-        lane.run(lambda: K.conv_wgrad(ba1, dc2, w2, 3, 3, 1, 1, defer=lane.folds), ba1, dc2, w2, block=bidx)
+        K.conv_wgrad(ba1, dc2, w2, 3, 3, 1, 1, defer=lane.folds)
     da1 = torch.empty_like(ba1)
     C1 = bc1.shape[-1]
     red1p = arena.take(C1, parts=K.bn_red_rows(ba1.numel() // C1))
@@ -651,14 +648,14 @@ def block_backward(trunk, blk: BasicBlock, sv, dx: torch.Tensor, grads, training
     # conv1 (+ downsample) -> dx of the block input (+ the preceding block's bn2 / downsample reductions)
     w1 = _grad(blk.conv1.weight, grads)
     if w1 is not None:
-        lane.run(lambda: K.conv_wgrad(xin, dc1, w1, 3, 3, s, 1, defer=lane.folds), xin, dc1, w1, block=bidx)
+        K.conv_wgrad(xin, dc1, w1, 3, 3, s, 1, defer=lane.folds)
     dxin = torch.empty_like(xin)
     Cin = xin.shape[-1]
     bnr, nxt = _bnr_target(prev[0], prev[1], arena) if prev is not None else (None, None)
     if cd is not None:
         wd = _grad(blk.downsample[0].weight, grads)
         if wd is not None:
-            lane.run(lambda: K.conv_wgrad(xin, dcd, wd, 1, 1, s, 0, defer=lane.folds), xin, dcd, wd, block=bidx)
+            K.conv_wgrad(xin, dcd, wd, 1, 1, s, 0, defer=lane.folds)
         if FUSED_DS_DGRAD and s == 2:  # the downsample's input gradient as an extra K segment of conv1's dgrad
             rows = K.conv_dgrad(dc1, trunk.packed(blk.conv1, Cin, True), dxin, 3, 3, s, 1, bnr=bnr,
                                 ds=(dcd, trunk.packed(blk.downsample[0], Cin, True)))
@@ -700,7 +697,7 @@ def trunk_backward_start(trunk, saved, dfeat, training, split, force_pack=False)
         # (still zeroed: leaving it unzeroed -- every row a fold reads is written first, the dgrads' reduction row
         # counts being exact -- measured +0.06 %, inside the noise, profiles/r06/step_ab_bwd_rows_exact)
         arena = _StatsArena(trunk, dev, floats=sum(_block_bwd_floats(sv) for sv in svs) + 2 * K.BN_RED_WS_ROWS * 64 * 2)
-        state = dict(dx=dx, pre=None, grads={}, arena=arena, i=len(svs) - 1, lane=_WgradLane(dev))
+        state = dict(dx=dx, pre=None, grads={}, arena=arena, i=len(svs) - 1, lane=_WgradLane())
         _backward_blocks(trunk, saved, state, max(split, trunk.backward_stop(), 0), training)
         state["lane"].join()  # the early-bucket hook (or the next graph segment) sees final layer4 gradients
         return state
@@ -713,7 +710,7 @@ def _backward_blocks(trunk, saved, state, lo, training):
         prev = (svs[i - 1], blocks[i - 1]) if i > 0 else None
         state["dx"], state["pre"] = block_backward(trunk, blocks[i], svs[i], state["dx"], state["grads"], training,
                                                    pre=state["pre"], prev=prev, arena=state["arena"],
-                                                   lane=state["lane"], bidx=i)
+                                                   lane=state["lane"])
         if FOLD_EVERY and i % FOLD_EVERY == 0 and i > 0:
             state["lane"].join()
         state["i"] = i - 1

@@ -570,7 +570,37 @@ def test_wgrad_split_k_groups(N, H, C, Kc, R, stride, pad):
     # same split count: only the in-workgroup split point differs
     assert (out[(8, 3)][0] - out[(4, 3)][0]).abs().max() <= 2e-5 * scale + 1e-6
     if P > 64:
-        assert K.wgrad_split_count(P, 3) <= 3
+        assert K.wgrad_plan(N, H, H, C, creal, Kc, R, R, stride, pad, 8, 3).slabs <= 3
+
+
+@pytest.mark.parametrize("variant", [4, 8])
+@pytest.mark.parametrize("N,H,C,Kc,R,stride,pad,splits,slabs", [(5, 14, 64, 128, 3, 1, 1, 64, 16),
+                                                                (3, 7, 64, 64, 1, 2, 0, 3, 1)])
+def test_wgrad_ring_writes_the_planned_slabs(variant, N, H, C, Kc, R, stride, pad, splits, slabs):
+    """A ring launch (mer_conv_wgrad_partials) writes exactly the slabs K.wgrad_plan names -- 980 pixels asked for 64
+    splits are 16 slabs of 64, 48 pixels asked for 3 are one -- and leaves the rest of the workspace alone; their sum
+    in slab order is the immediate fold's result bit for bit (up to 16 slabs it is one chain from slab 0 into a zero
+    dw)."""
+    from multimodalemotionrecognition_amd import kernels as K
+    from multimodalemotionrecognition_amd._lib import LIB
+
+    torch.manual_seed(21)
+    Ho = (H + 2 * pad - R) // stride + 1
+    x = torch.randn(N, H, H, C, device="cuda").bfloat16()
+    dy = torch.randn(N, Ho, Ho, Kc, device="cuda").bfloat16()
+    plan = K.wgrad_plan(N, H, H, C, C, Kc, R, R, stride, pad, variant, splits)
+    assert (plan.variant, plan.splits, plan.slabs, plan.ws_floats) == (variant, splits, slabs, splits * Kc * R * R * C)
+    ws = torch.full((splits, Kc, R * R * C), float("nan"), device="cuda")
+    LIB("mer_conv_wgrad_partials", N, H, H, C, Kc, R, R, stride, pad, x.data_ptr(), dy.data_ptr(), splits,
+        ws.data_ptr(), variant, K.stream_ptr())
+    assert torch.isfinite(ws[:plan.slabs]).all()
+    assert torch.isnan(ws[plan.slabs:]).all()
+    dw = torch.zeros(Kc, C, R, R, device="cuda")
+    K.conv_wgrad(x, dy, dw, R, R, stride, pad, variant=variant, splits=splits)
+    total = torch.zeros(Kc, R * R * C, device="cuda")
+    for z in range(plan.slabs):
+        total = total + ws[z]
+    assert torch.equal(total.view(Kc, R * R, C).permute(0, 2, 1).reshape(Kc, C, R, R), dw)
 
 
 def test_wgrad_fold_batch_matches_immediate_fold():

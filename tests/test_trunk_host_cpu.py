@@ -1,11 +1,16 @@
 """Host-side logic of the trunk backward's deferred weight-gradient folds (no GPU): the stem's slab-column map and
 the fold table the batched launch receives."""
+import subprocess
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
 
 from multimodalemotionrecognition_amd import kernels as K
 from multimodalemotionrecognition_amd.video import S2D_CH, _stem_wgrad_index, _stem_wgrad_map
+
+ROOT = Path(__file__).resolve().parents[1]
 
 
 def test_stem_wgrad_map_inverts_the_gather_index():
@@ -36,11 +41,22 @@ def test_wgrad_folds_table_and_split_count():
     dw = torch.zeros(2)
     f.add(ws, dw, 64, 64, 64, 9, 7)
     assert len(f.rows) == 1 and f.rows[0][3:] == [64, 64, 64, 9, 7]
-    for P, splits in ((200704, 154), (4096, 6), (1000, 64), (100, 3), (64, 1), (65, 2)):
-        eff = K.wgrad_split_count(P, splits)
+    from multimodalemotionrecognition_amd._lib import lib_path
+    if not lib_path().exists():  # the plan is the library's (host-only: no GPU needed)
+        subprocess.run(["make", "-C", str(ROOT / "multimodalemotionrecognition_amd" / "csrc"), "-j8"], check=True)
+
+    def slabs(N, H, W, splits):  # a 1x1 / stride-1 conv of N*H*W output pixels
+        p = K.wgrad_plan(N, H, W, 64, 64, 64, 1, 1, 1, 0, variant=4, splits=splits)
+        assert (p.variant, p.splits, p.ws_floats) == (4, splits, splits * 64 * 64)
+        return p.slabs
+
+    for (N, H, W), splits in (((64, 56, 56), 154), ((1, 64, 64), 6), ((10, 10, 10), 64), ((1, 10, 10), 3),
+                              ((1, 8, 8), 1), ((65, 1, 1), 2)):
+        P = N * H * W
+        eff = slabs(N, H, W, splits)
         pps = (-(-P // splits) + 63) // 64 * 64  # pixels per split, a multiple of 64
         assert 1 <= eff <= splits and pps % 64 == 0 and (eff - 1) * pps < P <= eff * pps  # none empty, all covered
-    assert K.wgrad_split_count(1000, 64) == 16  # 64 asked, 16-pixel splits rounded up to 64: 16 non-empty
+    assert slabs(10, 10, 10, 64) == 16  # 64 asked, 16-pixel splits rounded up to 64: 16 non-empty
     assert np.array(f.rows, dtype=np.int64).shape == (1, 8)
 
 

@@ -7,7 +7,8 @@ entries are used (K.conv_wgrad(..., defer=), WgradFolds.flush), so the file also
 library given through MER_HIP_LIB.
 
 Split counts sit on both sides of the two SG thresholds (12 | 13, 48 | 49) with tails that are no multiple of 4 or 8.
-N images whose output map is 8x8 and splits = N make wgrad_split_count(64 * N, N) == N, so N is the slab count.
+N images whose output map is 8x8 and splits = N make the planned slabs of 64 * N pixels in N splits N, so N is the
+slab count.
 Shapes: a 3x3 conv whose dw runs are 16-byte aligned (also through a dw view one float off, so the run starts and ends
 inside a 16-byte vector), a 1x1 / stride-2 conv, a 7x7 / stride-2 conv with Creal = 3 of 8 channels (147 floats per
 output channel: every alignment, c >= Creal dropped), and the stem's map record (4x4 space-to-depth slabs gathered into
@@ -81,7 +82,7 @@ def _records(N):
     folds.rows, folds.keep = [], []
     full = []
     for row, ws, (init, out, Kc, C, creal, R, m) in zip(rows, keep[0::3], recs):
-        assert row[7] == N == K.wgrad_split_count(64 * N, N)  # the slab count the fold is told
+        assert row[7] == N == K.wgrad_plan(N, 8, 8, 64, 64, 64, 1, 1, 1, 0, 4, N).slabs  # the slab count the fold is told
         full.append((init, out, ws.view(N, Kc, R * R * C), Kc, C, creal, R, m))
     torch.cuda.synchronize()
     return rows, keep, full

@@ -99,14 +99,14 @@ def test_strip_wgrad_error_vs_ring(N, H, W, C, Kc):
 
 @pytest.mark.parametrize("N,H,W,C,Kc", [(3, 5, 5, 64, 64), (5, 14, 14, 128, 128)])
 def test_strip_wgrad_repeatable_and_split_count(N, H, W, C, Kc):
-    """Two launches give equal slabs and an equal dw; the launch writes exactly wgrad_strip_split_count slabs (every
-    split non-empty, never more than asked)."""
+    """Two launches give equal slabs and an equal dw; the launch writes exactly the planned slabs (every split
+    non-empty, never more than asked)."""
     from multimodalemotionrecognition_amd import kernels as K
 
     x, dy, _, _ = _case(N, H, W, C, Kc)
     for v in STRIP:
         for splits in (4, 7, 1000):
-            eff = K.wgrad_strip_split_count(N, H, splits)
+            eff = K.wgrad_plan(N, H, W, C, C, Kc, 3, 3, 1, 1, v, splits).slabs
             assert 1 <= eff <= splits
             a, b = _partials(x, dy, v, splits, min(splits, eff + 1)), _partials(x, dy, v, splits, min(splits, eff + 1))
             assert torch.isfinite(a[:eff]).all() and torch.isnan(a[eff:]).all(), (v, splits)
@@ -130,7 +130,7 @@ def test_strip_wgrad_deferred_fold():
         ref = _wgrad(x, dy, v, splits, init.clone())
         out = init.clone()
         K.conv_wgrad(x, dy, out, 3, 3, 1, 1, variant=v, splits=splits, defer=folds)
-        assert folds.rows[-1][7] == K.wgrad_strip_split_count(N, H, splits)
+        assert folds.rows[-1][7] == K.wgrad_plan(N, H, W, C, C, Kc, 3, 3, 1, 1, v, splits).slabs
         pairs.append((ref, out, init, splits))
     torch.cuda.synchronize()
     assert all(torch.equal(o, i) for _, o, i, _ in pairs)  # nothing folded before the flush

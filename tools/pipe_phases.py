@@ -114,20 +114,16 @@ def run_wgrad(variants, bound=False):
         P = NF * Ho * Ho
         x = (torch.rand(NF, H, H, C, device="cuda") * 2 - 1).bfloat16()
         dy = (torch.rand(NF, Ho, Ho, Kc, device="cuda") * 2 - 1).bfloat16()
-        tiles = ((Kc + 127) // 128) * ((9 * C + 127) // 128)
         for v in variants:
-            if v in K._WGRAD_STRIP_KB:
-                if st != 1 or Kc % K._WGRAD_STRIP_KB[v]:
-                    continue
-                stiles = (C // 64) * (Kc // K._WGRAD_STRIP_KB[v])
-                splits = max(1, min(K._WGRAD_STRIP_WGS // stiles, NF * (H + 1) * (H + 1) // 1024))
+            try:
+                splits = K.wgrad_plan(NF, H, H, C, C, Kc, 3, 3, st, 1, variant=v).splits
+            except K.MerKernelError:  # a shape the strip kernel (9, 10) does not take
+                continue
+            if v in (9, 10):
                 rows = NF * (H + 1)
                 steps = -(-(-(-rows // splits)) * (H + 1) // 64)
             else:
-                kg = 2 if v == 8 else 1
-                splits = int(max(1, min(-(-K._WGRAD_WGS // (kg * tiles)),
-                                        P // (kg * K._wgrad_min_pix(Kc * 9 * C, tiles)))))
-                steps = -(-(-(-P // splits)) // 64) / kg
+                steps = -(-(-(-P // splits)) // 64) / (2 if v == 8 else 1)
             dw = torch.zeros(Kc, C, 3, 3, device="cuda")
             fn = lambda: K.conv_wgrad(x, dy, dw, 3, 3, st, 1, variant=v, splits=splits)  # noqa: E731
             per_step = []
