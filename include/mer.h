@@ -905,6 +905,22 @@ int mer_rows_gather(int n_src, int n_out, int D, const float* src, const int* id
  * top1 int32 [Nw]. */
 int mer_timeline_smooth(int Nw, int C, int radius, const float* probs, float* smoothed, int* top1, void* stream);
 
+/* ============================ face-box crops (clips.crop_resize_frames) ============================
+ * Ragged crop-and-resize: output n is made from one rectangle of one image.  frames: a device byte buffer of
+ * frames_bytes bytes holding tightly packed RGB uint8 images [H0][W0][3] of differing sizes.  desc: DEVICE int64
+ * [n_out][8], row n = {byte offset of the image, H0, W0, x1, y1, x2, y2, 0}; (x1, y1, x2, y2) is the final, already
+ * padded and clipped rectangle, half-open as frame[y1:y2, x1:x2].  mode 0: out fp32 [n_out][3][S][S], normalised as
+ * mer_frames_resize_normalize; mode 1: out uint8 [n_out][S][S][3] as mer_frames_resize_u8.  Output n is bit for bit
+ * what those give for the contiguous copy of the rectangle: scales and tap clamps from the rectangle's size (no pixel
+ * outside it is read), the exact-2x INTER_AREA path when the rectangle is 2S x 2S, rows W0 * 3 bytes apart.
+ * As for the timeline kernels, the Python wrapper validates every row on the host and the kernel clamps image and
+ * rectangle into the buffer, so no launch reads outside frames.  NULL frames / desc / out, S < 1, n_out < 0,
+ * frames_bytes < 3 or another mode: hipErrorInvalidValue; n_out == 0: 0 without a launch.  Any n_out: launched in
+ * chunks of 65535 frames (grid z). */
+int mer_frames_crop_resize(const void* frames, long frames_bytes, int n_out, const long* desc, int S, int mode,
+                           float mean0, float mean1, float mean2, float std0, float std1, float std2, void* out,
+                           void* stream);
+
 /* ============================ live streaming sessions (streaming.py) ============================
  * Per-session device rings written once and read by every window.  Scalar arguments are checked here, device
  * descriptor arrays by the Python wrappers on the host; the kernels clamp as well. */

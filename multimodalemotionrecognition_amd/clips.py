@@ -24,9 +24,14 @@ decoded uint8 frames / raw waveforms cross PCIe and the batch is assembled in HB
   batch: ragged clips at their native rates resampled (the stream's arithmetic, bit for bit), padded / cropped and
   mixed with the bar-noise track at the drawn SNR (``draw_audio_augment``: the host's draws in the host's order).
 
-Decoding (cv2.VideoCapture / librosa) and face detection / crop stay on the host, and so does the audio path of the
+* ``crop_rects`` / ``pack_frames`` / ``crop_resize_frames`` -- the face-box crop (face_crop.py:151-190) and the resize
+  in one ragged launch: images of differing sizes in one buffer, one rectangle per output frame, the bits of resizing
+  the host-cropped copy.  ``gather_preprocess_frames(..., rects=)``, the streaming sessions' ``add_frame(bbox=)`` and
+  ``ClipLoader(device_video=True)`` run on it.
+
+Decoding (cv2.VideoCapture / librosa) and face detection stay on the host, and so does the audio path of the
 default ``ClipLoader``.  Kernels: ``csrc/clips.hip``, ``csrc/mel.hip``, ``csrc/timeline.hip``,
-``csrc/stream.hip``, ``csrc/audio_clips.hip``;
+``csrc/stream.hip``, ``csrc/audio_clips.hip``, ``csrc/frame_crop.hip``;
 CPU restatements:
 ``oracle/clips_ref.py``, ``tests/mel_ref.py``.
 """
@@ -62,22 +67,197 @@ def preprocess_frames(frames: torch.Tensor, size: int = 112, out: torch.Tensor =
     return out
 
 
-def gather_preprocess_frames(frames: torch.Tensor, idx, size: int = 112) -> torch.Tensor:
+def gather_preprocess_frames(frames: torch.Tensor, idx, size: int = 112, rects=None) -> torch.Tensor:
     """``preprocess_frames(frames.index_select(0, idx), size)``, bit for bit, without the gathered uint8 copy: output
     ``n`` is made from frame ``idx[n]`` of the decoded recording ``[N, H, W, 3]`` (repeats and any order allowed), one
     launch for all of them.  ``idx``: a sequence or an int32 / int64 tensor; every value is checked against ``[0, N)``
-    on the host (``ValueError``) before anything is launched."""
+    on the host (``ValueError``) before anything is launched.
+
+    ``rects``: one final rectangle ``(x1, y1, x2, y2)`` per output (``crop_rects``); output ``n`` is then the
+    preprocessing of ``frames[idx[n], y1:y2, x1:x2]``, through ``crop_resize_frames``.  ``None`` keeps the entry point
+    and the bits this function always had."""
     if not frames.is_cuda:
         raise RuntimeError("gather_preprocess_frames runs on the MI355X kernels; move the frames to the GPU")
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError("frames must be uint8 [N, H, W, 3] (RGB)")
     frames = frames.contiguous()
     N, H, W, _ = frames.shape
+    if rects is not None:
+        host = torch.as_tensor(idx)
+        if host.numel() == 0 and host.dim() == 1:
+            host = host.to(torch.int64)
+        if host.dtype not in (torch.int32, torch.int64) or host.dim() != 1:
+            raise ValueError(f"frame index must be a 1-D int32 / int64 array, got {host.dtype} {tuple(host.shape)}")
+        host = host.cpu().to(torch.int64)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= N):
+            raise ValueError(f"frame index outside [0, {N}): min {int(host.min())}, max {int(host.max())}")
+        rows = crop_rows(host * (H * W * 3), H, W, rects)
+        return crop_resize_frames(frames.view(-1), rows, size)
     dix = K.checked_index(idx, N, frames.device, "frame index")
     U = dix.numel()
     out = torch.empty(U, 3, size, size, device=frames.device, dtype=torch.float32)
     if U:
         K.LIB("mer_frames_gather_resize_normalize", N, H, W, frames.data_ptr(), H * W * 3, U, dix.data_ptr(), size,
+              *IMAGENET_MEAN, *IMAGENET_STD, out.data_ptr(), K.stream_ptr())
+    return out
+
+
+CROP_MAX_SIDE = 1 << 24  # csrc/frame_crop.hip keeps W * 3 and the tap offsets inside an int
+CROP_MAX_SIZE = 16 * 65535  # its grid holds one band of 16 output rows per y block
+
+
+def _int_table(a, cols: int, what: str):
+    """``a`` as a host int64 numpy array ``[n, cols]``; anything that is not an integer array of that shape:
+    ``ValueError``."""
+    import numpy as np
+
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    try:
+        t = np.asarray(a)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be an integer array [n, {cols}]") from None
+    if t.size == 0 and t.ndim <= 2:
+        t = t.reshape(0, cols).astype(np.int64)
+    if t.dtype.kind not in "iu" or t.ndim != 2 or t.shape[1] != cols:
+        raise ValueError(f"{what} must be an integer array [n, {cols}], got {t.dtype} {tuple(t.shape)}")
+    return t.astype(np.int64)
+
+
+def crop_rects(H: int, W: int, boxes, pad_ratio: float = 0.3):
+    """Raw detector boxes ``(x1, y1, x2, y2)`` of ``H x W`` frames -> the rectangles the frames are cropped to, host
+    int64 ``[n, 4]``, half-open as ``frame[y1:y2, x1:x2]``: ``crop_with_padding``'s box (face_crop.py:151-190, each
+    side padded by ``int(side * pad_ratio)``, clipped to the frame) through ``data.face_crop_box``.  ``boxes``: a
+    sequence of boxes, an integer array ``[n, 4]``, and ``None`` in place of a box where nothing was detected.  A
+    missing box, or a rectangle that comes out empty (``x2 <= x1`` or ``y2 <= y1``), means the whole frame ``(0, 0, W,
+    H)`` -- ``data.select_frames``'s rule.  Host only: no device is touched."""
+    import numpy as np
+
+    from .data import face_crop_box
+
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"frame size must be positive, got {H} x {W}")
+    boxes = list(boxes) if not isinstance(boxes, (np.ndarray, torch.Tensor)) else _int_table(boxes, 4, "boxes")
+    out = np.empty((len(boxes), 4), dtype=np.int64)
+    for n, b in enumerate(boxes):
+        rect = (0, 0, W, H)
+        if b is not None:
+            try:
+                vals = [int(v) for v in b]
+                exact = all(int(v) == v for v in b)
+            except (TypeError, ValueError):
+                raise ValueError(f"box {n} must be four integers (x1, y1, x2, y2), got {b!r}") from None
+            if len(vals) != 4 or not exact or any(abs(v) >= 2 ** 30 for v in vals):
+                raise ValueError(f"box {n} must be four integers (x1, y1, x2, y2) below 2^30, got {b!r}")
+            x1, y1, x2, y2 = face_crop_box(H, W, vals, pad_ratio)
+            if x2 > x1 and y2 > y1:
+                rect = (x1, y1, x2, y2)
+        out[n] = rect
+    return out
+
+
+def crop_rows(offsets, H, W, rects):
+    """The descriptor table of ``crop_resize_frames``, host int64 ``[n, 8]``: row ``n`` = ``{offsets[n], H[n], W[n],
+    x1, y1, x2, y2, 0}``.  ``H`` / ``W``: one int for all rows or one per row; ``rects`` ``[n, 4]``."""
+    import numpy as np
+
+    rects = _int_table(rects, 4, "rects")
+    n = rects.shape[0]
+    rows = np.zeros((n, 8), dtype=np.int64)
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.cpu().numpy()
+    try:
+        if np.size(offsets) != n:
+            raise ValueError
+        rows[:, 0] = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        rows[:, 1], rows[:, 2] = np.asarray(H, dtype=np.int64), np.asarray(W, dtype=np.int64)
+    except (TypeError, ValueError):
+        raise ValueError(f"crop_rows: {n} rectangles need {n} offsets and one or {n} heights / widths") from None
+    rows[:, 3:7] = rects
+    return rows
+
+
+def pack_frames(arrays, device="cuda"):
+    """Decoded frames of differing sizes -> one device byte buffer: ``arrays`` is a list of uint8 host arrays (numpy or
+    tensors) ``[T_i, H_i, W_i, 3]``; every image is copied once into ONE pinned staging buffer, tightly packed in list
+    order (``stage_frames``), which crosses PCIe in one asynchronous copy (``_h2d``'s pinned route: the caching host
+    allocator keeps the block until the copy has run).  Returns ``(buffer, offsets)``: the 1-D uint8 device tensor and
+    the byte offset of every image, ``sum(T_i)`` ints in order."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pack_frames stages frames for the MI355X kernels; pass device='cuda'")
+    stage, offsets = stage_frames(arrays)
+    return stage.to(dev, non_blocking=True), offsets
+
+
+def stage_frames(arrays):
+    """The host half of ``pack_frames``: ``(pinned 1-D uint8 host tensor, byte offset of every image)``.  A loader
+    calls it on its producer thread, so the gather into pinned memory stays off the thread that feeds the device."""
+    import numpy as np
+
+    flat, offsets, total = [], [], 0
+    for a in arrays:
+        t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+        if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
+            raise ValueError("pack_frames takes uint8 host arrays [T, H, W, 3] (RGB)")
+        T, H, W, _ = t.shape
+        offsets += [total + i * H * W * 3 for i in range(T)]
+        total += T * H * W * 3
+        flat.append(t.contiguous().view(-1))
+    if not total:
+        raise ValueError("pack_frames: no pixels to pack")
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    torch.cat(flat, out=stage)
+    return stage, offsets
+
+
+def crop_resize_frames(buffer: torch.Tensor, rows, size: int = 112, u8: bool = False,
+                       out: torch.Tensor = None) -> torch.Tensor:
+    """Ragged crop-and-resize, one launch (mer_frames_crop_resize): ``buffer`` is a 1-D uint8 device tensor of tightly
+    packed RGB images (``pack_frames``, or a decoded recording viewed flat), ``rows`` the host int64 table ``[n, 8]``
+    of ``crop_rows`` (``[n, 7]`` is taken too): image byte offset, ``H0``, ``W0`` and the final half-open rectangle
+    ``(x1, y1, x2, y2)``.  Output ``n`` is ``preprocess_frames`` (``u8=True``: ``resize_frames_u8``) of the contiguous
+    copy of ``image[y1:y2, x1:x2]``, bit for bit: fp32 ``[n, 3, size, size]`` or uint8 ``[n, size, size, 3]``, written
+    into ``out`` when given.  Every row is checked against the buffer on the host (``ValueError``) before the table is
+    uploaded; images may repeat and overlap."""
+    import numpy as np
+
+    size = int(size)
+    if not 1 <= size <= CROP_MAX_SIZE:
+        raise ValueError(f"size must be in [1, {CROP_MAX_SIZE}], got {size}")
+    if not isinstance(buffer, torch.Tensor) or buffer.dtype != torch.uint8 or buffer.dim() != 1 \
+            or not buffer.is_contiguous():
+        raise ValueError("buffer must be a contiguous 1-D uint8 tensor")
+    t = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    if t.ndim == 2 and t.shape[1] == 7 and t.dtype.kind in "iu":
+        t = np.concatenate([t, np.zeros((t.shape[0], 1), dtype=t.dtype)], axis=1)
+    t = _int_table(t, 8, "rows")
+    n, nbytes = int(t.shape[0]), int(buffer.numel())
+    if n >= 2 ** 31:
+        raise ValueError(f"{n} output frames do not fit one call")
+    if n:
+        off, H0, W0, x1, y1, x2, y2, last = (t[:, c] for c in range(8))
+        if int(H0.min()) < 1 or int(W0.min()) < 1 or int(H0.max()) > CROP_MAX_SIDE or int(W0.max()) > CROP_MAX_SIDE:
+            raise ValueError(f"image sizes must be in [1, {CROP_MAX_SIDE}]")
+        bad = (off < 0) | (off + H0 * W0 * 3 > nbytes) | (x1 < 0) | (y1 < 0) | (x2 <= x1) | (y2 <= y1) | (x2 > W0) \
+            | (y2 > H0) | (last != 0)
+        if bool(bad.any()):
+            b = int(np.argmax(bad))
+            raise ValueError(f"row {b} {t[b].tolist()}: the image must lie inside the buffer of {nbytes} bytes and the "
+                             "rectangle, non-empty, inside the image (last column 0)")
+    if not buffer.is_cuda:
+        raise RuntimeError("crop_resize_frames runs on the MI355X kernels; move the buffer to the GPU")
+    dev = buffer.device
+    shape = (n, size, size, 3) if u8 else (n, 3, size, size)
+    dtype = torch.uint8 if u8 else torch.float32
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=dtype)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"crop_resize_frames out must be contiguous {dtype} {list(shape)} on {dev}")
+    if n:
+        desc = _h2d(torch.from_numpy(np.ascontiguousarray(t)), dev)
+        K.LIB("mer_frames_crop_resize", buffer.data_ptr(), nbytes, n, desc.data_ptr(), size, int(bool(u8)),
               *IMAGENET_MEAN, *IMAGENET_STD, out.data_ptr(), K.stream_ptr())
     return out
 

@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void frames_resize_normalize_kernel(int H0, in
                                                                       float sd1, float sd2, float* __restrict__ dst) {
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
   if (x >= S) return;
-  resize_normalize_pixel(src + (long)n * frame_stride, H0, W0, S, x, y, n, scale_y, scale_x,
+  resize_normalize_pixel(src + (long)n * frame_stride, (long)W0 * 3, H0, W0, S, x, y, n, scale_y, scale_x,
                          FrameNorm{m0, m1, m2, sd0, sd1, sd2}, dst);
 }
 
@@ -27,11 +27,8 @@ __global__ __launch_bounds__(256) void frames_resize_u8_kernel(int H0, int W0, i
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
   if (x >= S) return;
   int v[3];
-  resize_pixel(src + (long)n * frame_stride, H0, W0, S, x, y, scale_y, scale_x, v);
-  uint8_t* o = dst + (((long)n * S + y) * S + x) * 3;
-  o[0] = (uint8_t)v[0];
-  o[1] = (uint8_t)v[1];
-  o[2] = (uint8_t)v[2];
+  resize_pixel(src + (long)n * frame_stride, (long)W0 * 3, H0, W0, S, x, y, scale_y, scale_x, v);
+  store_u8(v, S, x, y, n, dst);
 }
 
 // cv::borderInterpolate(p, n, BORDER_REFLECT_101) (cv2.GaussianBlur's default border): gfedcb|abcdefgh|gfedcba

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void frames_gather_resize_normalize_kernel(
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, n = n0 + blockIdx.z;
   if (x >= S) return;
   const int f = clamp_index(idx[n], n_src);
-  resize_normalize_pixel(src + (long)f * frame_stride, H0, W0, S, x, y, n, scale_y, scale_x, nm, dst);
+  resize_normalize_pixel(src + (long)f * frame_stride, (long)W0 * 3, H0, W0, S, x, y, n, scale_y, scale_x, nm, dst);
 }
 
 // one thread per 16 bytes of the output

@@ -16,6 +16,8 @@ code (``host/mer_io.cpp`` -> ``libmer_io.so``, C-ABI ``include/mer_io.h``) and t
   release the GIL), each rank takes a disjoint shard (DP), and batches land in HBM as
   ``[B, 8, 3, 112, 112]`` / ``[B, 1, 48000]`` / labels.  ``device_audio=True`` leaves only the WAV decode and the
   draws to the workers: resampling, pad / crop and the noise mix run on the device (``clips.assemble_waveforms``).
+  ``device_video=True`` packs a batch's cropped clips into one pinned buffer: one copy and one ragged resize launch
+  per batch (``clips.crop_resize_frames``) instead of one of each per clip.
 """
 from __future__ import annotations
 
@@ -251,13 +253,21 @@ class ClipLoader:
     PCIe as one packed pinned copy per input rate and ``clips.assemble_waveforms`` resamples, pads / crops and mixes
     the noise there (the track is uploaded once per loader).  Against the default it differs by the resampler's
     rounding (fp32 fmaf sums against the host's double-rounded taps) and, with no bar-noise track, by the Gaussian
-    fallback's generator; video, labels and every draw are the same.  The default (``False``) is the host path."""
+    fallback's generator; video, labels and every draw are the same.  The default (``False``) is the host path.
+
+    ``device_video=True`` batches the video side of the assembly.  The workers do what they always did (sample on the
+    host and apply the face crop there, so only the crops cross PCIe, never whole frames); the producer thread then
+    gathers the batch's crops, which differ in size, into ONE pinned buffer (``clips.stage_frames``), and ``_assemble``
+    issues one asynchronous host-to-device copy and ONE ragged launch (``clips.crop_resize_frames``: fp32 for eval,
+    uint8 feeding ``augment_clips`` for the train split) instead of one blocking pageable copy and one launch per
+    clip.  Batches are bit-identical to the default; items, draw order and ``meta`` are unchanged."""
 
     def __init__(self, items: Sequence[Tuple], batch_size: int = 32, num_frames: int = 8, size: int = 112,
                  sample_rate: int = 16000, duration_sec: float = 3.0, rank: int = 0, world: int = 1,
                  workers: int = 8, prefetch: int = 2, device="cuda", shuffle: bool = False, seed: int = 0,
                  drop_last: bool = True, augment: bool = False, bar_noise: Optional[np.ndarray] = None,
-                 pad_shards: bool = True, audio_features: str = "wav", n_mels: int = 64, device_audio: bool = False):
+                 pad_shards: bool = True, audio_features: str = "wav", n_mels: int = 64, device_audio: bool = False,
+                 device_video: bool = False):
         self.all_items = list(items)
         if audio_features not in ("wav", "mel"):
             raise ValueError(f"audio_features must be 'wav' or 'mel', got {audio_features!r}")
@@ -274,8 +284,11 @@ class ClipLoader:
         self.pad_shards = bool(pad_shards)
         self.device_audio = bool(device_audio)
         self._bar_dev = None  # the bar-noise track on the device, uploaded once (device_audio)
+        self.device_video = bool(device_video)
         if self.device_audio and self.device.type != "cuda":
             raise RuntimeError("ClipLoader(device_audio=True) runs on the MI355X kernels; pass device='cuda'")
+        if self.device_video and self.device.type != "cuda":
+            raise RuntimeError("ClipLoader(device_video=True) runs on the MI355X kernels; pass device='cuda'")
         self.epoch = 0
 
     @property
@@ -294,9 +307,31 @@ class ClipLoader:
         n = self.num_samples()
         return n // self.B if self.drop_last else -(-n // self.B)
 
-    def _assemble(self, decoded):
+    def _stage_video(self, decoded):
+        """``device_video``, host half (the producer thread): the batch's cropped clips, which differ in size, gathered
+        into ONE pinned buffer, and the descriptor table of the ragged resize -- whole images: the workers cropped
+        them."""
+        stage, offsets = clips.stage_frames([d[0] for d in decoded])
+        hw = np.array([d[0].shape[1:3] for d in decoded for _ in range(d[0].shape[0])], dtype=np.int64)
+        rects = np.concatenate([np.zeros_like(hw), hw[:, ::-1]], axis=1)
+        return stage, clips.crop_rows(offsets, hw[:, 0], hw[:, 1], rects)
+
+    def _assemble_video(self, decoded, staged=None):
+        """``device_video``, device half: one host-to-device copy of the pinned buffer and one ragged resize launch
+        over all ``B * T`` frames (fp32 for eval, uint8 feeding ``augment_clips`` for the train split)."""
+        stage, rows = staged if staged is not None else self._stage_video(decoded)
+        buf = stage.to(self.device, non_blocking=True)  # the caching host allocator keeps the block until it ran
+        B = len(decoded)
+        if self.augment:
+            u8 = clips.crop_resize_frames(buf, rows, self.size, u8=True)
+            return clips.augment_clips(u8.view(B, self.T, self.size, self.size, 3), [d[4] for d in decoded])
+        return clips.crop_resize_frames(buf, rows, self.size).view(B, self.T, 3, self.size, self.size)
+
+    def _assemble(self, decoded, staged=None):
         # frames of one batch may differ in size (per-clip crops): resize each clip's frames on the device
-        if self.augment:  # resized uint8 clips, then ONE augmentation + normalisation launch with per-clip draws
+        if self.device_video:
+            video = self._assemble_video(decoded, staged)
+        elif self.augment:  # resized uint8 clips, then ONE augmentation + normalisation launch with per-clip draws
             u8 = torch.empty(len(decoded), self.T, self.size, self.size, 3, device=self.device, dtype=torch.uint8)
             for i, d in enumerate(decoded):
                 clips.resize_frames_u8(torch.from_numpy(d[0]).to(self.device), self.size, out=u8[i])
@@ -337,7 +372,8 @@ class ClipLoader:
                         if stop.is_set():
                             return
                         decoded = list(ex.map(self._decode_epoch(epoch), [(int(i), self.all_items[i]) for i in b]))
-                        out_q.put(("ok", decoded))
+                        staged = self._stage_video(decoded) if self.device_video else None
+                        out_q.put(("ok", (decoded, staged)))
             except BaseException as e:  # surfaced to the consumer
                 out_q.put(("err", e))
             out_q.put(("end", None))
@@ -351,7 +387,7 @@ class ClipLoader:
                     return
                 if kind == "err":
                     raise val
-                yield self._assemble(val)
+                yield self._assemble(*val)
         finally:
             stop.set()
 

@@ -147,7 +147,8 @@ class TorchModelRunner:
     def predict_timeline(self, frames_u8: Optional[torch.Tensor], waveform: Optional[torch.Tensor], fps, *,
                          window_sec: float = 3.0, hop_sec: float = 1.0, frames_per_window: int = 8,
                          frame_grid: str = "window", include_tail: bool = False, smooth_radius: int = 0,
-                         max_windows_per_batch: int = 64, sample_rate: int = SAMPLE_RATE) -> Dict[str, Any]:
+                         max_windows_per_batch: int = 64, sample_rate: int = SAMPLE_RATE, face_boxes=None,
+                         pad_ratio: float = 0.3, debug: bool = False) -> Dict[str, Any]:
         """One prediction per window over a whole decoded recording, every frame encoded once.
 
         ``frames_u8`` ``[N, H, W, 3]`` uint8 RGB at ``fps`` and the mono 16 kHz ``waveform`` (fp32, any shape), host
@@ -168,11 +169,32 @@ class TorchModelRunner:
 
         ``sample_rate``: the waveform's rate.  Any rate other than 16000 resamples the whole recording once on the
         device (``clips.resample_clips``, scipy ``resample_poly``'s filter) before the windows are planned; the result
-        is ``predict_timeline`` of that resampled waveform.  At 16000 nothing changes."""
+        is ``predict_timeline`` of that resampled waveform.  At 16000 nothing changes.
+
+        ``face_boxes``: the face crop of the reference's ``use_face_crop`` (``crop_with_padding``, each side padded
+        by ``pad_ratio``), for a checkpoint trained on face crops.  ``None``: whole frames, the bits this method
+        always gave.  One raw detector box ``(x1, y1, x2, y2)``: every frame is cropped to it.  An integer array
+        ``[N, 4]``: one box per decoded frame, an empty row meaning "no detection" (the whole frame is used).  Only
+        the rectangles of the unique sampled frames are computed (``clips.crop_rects``); each such frame is cropped
+        with its OWN box on the device (``clips.gather_preprocess_frames(..., rects=...)``) and still encoded once.
+        This DEPARTS from the reference, which detects once per window and reuses that box for the window's frames
+        (preprocess.py ``load_video_frames``): here a box belongs to a frame, because frames are shared between
+        windows.  With one box for the recording, or boxes constant over a window, the two coincide.  Face
+        detection itself is the caller's.  A ``face_boxes`` of another shape or dtype, or boxes given to an
+        audio-only checkpoint, raise ``ValueError`` before any device work.
+
+        ``debug=True`` adds ``debug``: the preprocessed unique frames ``[U, 3, 112, 112]`` (device), ``unique_idx``,
+        ``inverse``, the ``rects`` used (or None) and ``trunk_batches``, the frame count of every trunk call."""
         from . import clips
         from . import kernels as K
-        from .timeline import plan_windows
+        from .timeline import checked_face_boxes, plan_windows
 
+        if face_boxes is not None:
+            if self.fusion_mode == "audio":
+                raise ValueError("face_boxes given to an audio-only checkpoint: it reads no frames")
+            if frames_u8 is None or frames_u8.dim() != 4:
+                raise ValueError("frames_u8 must be uint8 [N, H, W, 3] (RGB)")
+            boxes = checked_face_boxes(face_boxes, int(frames_u8.shape[0]))
         if int(sample_rate) != SAMPLE_RATE:
             clips.resample_ratio(sample_rate, SAMPLE_RATE)  # refuses a non-positive rate before any device work
         if self.device.type != "cuda":
@@ -208,13 +230,19 @@ class TorchModelRunner:
         Nw, T = plan.num_windows, plan.frames_per_window
         U = int(plan.unique_idx.numel()) if use_video else 0
         with torch.inference_mode():
-            v_feat = audio = None
+            v_feat = audio = x = rects = None
+            trunk_batches = []
             if use_video:
                 frames = frames_u8 if frames_u8.is_cuda else clips._h2d(frames_u8.contiguous(), self.device)
-                x = clips.gather_preprocess_frames(frames, plan.unique_idx)
+                if face_boxes is not None:  # the unique frames' own boxes -> their rectangles, host arithmetic
+                    own = boxes[plan.unique_idx.long().numpy()] if boxes.shape[0] == n_frames else \
+                        boxes.repeat(U, axis=0)
+                    rects = clips.crop_rects(frames.shape[1], frames.shape[2], own, pad_ratio)
+                x = clips.gather_preprocess_frames(frames, plan.unique_idx, rects=rects)
                 vnet = self.model if self.fusion_mode == "video" else self.model.video_model
                 step = chunk_w * T
                 feats = [vnet.backbone(x[i:i + step]).reshape(-1, vnet.embedding_dim) for i in range(0, U, step)]
+                trunk_batches = [min(step, U - i) for i in range(0, U, step)]
                 feats = feats[0] if len(feats) == 1 else torch.cat(feats)
                 v_feat = K.rows_gather(feats, plan.inverse.reshape(-1)).view(Nw, T, vnet.embedding_dim)
             if use_audio:
@@ -235,10 +263,14 @@ class TorchModelRunner:
             # one device-to-host copy: the class indices ride along as exactly representable floats
             host = torch.cat([probs, smoothed, top1.to(torch.float32)[:, None]], dim=1).cpu()
         C = probs.shape[1]
-        return {"probs": host[:, :C].contiguous(), "smoothed": host[:, C:2 * C].contiguous(),
-                "top1": host[:, 2 * C].to(torch.int32), "starts_sec": list(plan.starts_sec), "labels": self.labels,
-                "num_windows": Nw, "num_unique_frames": U, "num_frame_slots": Nw * T if use_video else 0,
-                "window_seconds": float(window_sec)}
+        res = {"probs": host[:, :C].contiguous(), "smoothed": host[:, C:2 * C].contiguous(),
+               "top1": host[:, 2 * C].to(torch.int32), "starts_sec": list(plan.starts_sec), "labels": self.labels,
+               "num_windows": Nw, "num_unique_frames": U, "num_frame_slots": Nw * T if use_video else 0,
+               "window_seconds": float(window_sec)}
+        if debug:
+            res["debug"] = dict(frames=x, unique_idx=plan.unique_idx, inverse=plan.inverse, rects=rects,
+                                trunk_batches=trunk_batches)
+        return res
 
 
     def open_stream_pool(self, max_sessions: int = 16, **kw):
@@ -281,7 +313,8 @@ def process_recording(runner: TorchModelRunner, frames_u8: Optional[torch.Tensor
     dict per window in ``process_batch``'s format, plus the window's ``start_sec`` and ``window_seconds`` (the keys
     of the streaming session's result, streaming.py:103-115).  With ``smooth_radius > 0`` each dict also carries
     ``smoothed``: the smoothed row in the same format, its top-1 the device's (lowest index on ties).
-    ``sample_rate``: the waveform's rate; any rate other than 16000 is resampled once on the device."""
+    ``sample_rate``: the waveform's rate; any rate other than 16000 is resampled once on the device.  ``face_boxes`` /
+    ``pad_ratio`` (in ``kw``) crop every frame to its face box first, as ``predict_timeline`` documents."""
     if int(sample_rate) != SAMPLE_RATE:
         kw["sample_rate"] = int(sample_rate)
     res = runner.predict_timeline(frames_u8, waveform, fps, **kw)

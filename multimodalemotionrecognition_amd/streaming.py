@@ -41,6 +41,14 @@ Departures from the reference, all from bounding what its deques leave unbounded
   window, which gives every window its own edge transient.  At 16 kHz input the two are identical.  An output sample
   waits for its newest input: ``10 * max(up, down) / up`` input samples of latency, nothing synthesised at the edge.
 
+Face crops.  ``add_frame(frame, ts, bbox=(x1, y1, x2, y2))`` takes the raw detector box of THAT frame: the frame is
+cropped to ``clips.crop_rects`` of it (``crop_with_padding``, the pool's ``pad_ratio``) and resized into its ring slot
+in one launch (mer_frames_crop_resize), with the bits of preprocessing the host-cropped frame.  This DEPARTS from the
+reference's ``create_session(use_face_crop=True)``, which detects once per window and reuses that box for the
+window's frames: here a box belongs to a frame, because a frame is preprocessed once and shared by every window that
+picks it.  With a box that is constant over a window the two coincide.  ``bbox=None`` keeps the whole-frame path;
+detection itself is the caller's.
+
 A pool and its sessions are driven from one thread and one HIP stream.
 """
 from __future__ import annotations
@@ -216,13 +224,21 @@ class StreamingSession:
     def last_prediction_ts(self) -> float:
         return self.state.last_prediction_ts
 
-    def add_frame(self, frame, timestamp: Optional[float] = None) -> None:
+    def add_frame(self, frame, timestamp: Optional[float] = None, bbox=None) -> None:
         """A decoded RGB frame, uint8 ``[H, W, 3]`` (numpy or tensor, host or device): preprocessed once into its
         ring slot.  A frame beyond ``max_frames`` overwrites the oldest; frames older than ``timestamp -
-        max_buffer_seconds`` are dropped."""
+        max_buffer_seconds`` are dropped.  ``bbox``: this frame's raw face box ``(x1, y1, x2, y2)``; the frame is
+        cropped to the padded box on the device (an empty box: the whole frame).  A malformed box is a ``ValueError``
+        before anything is stored."""
         t = checked_frame(frame)
         now = float(timestamp if timestamp is not None else time.monotonic())
-        self._open_pool()._store_frame(self, t, now)
+        pool = self._open_pool()
+        if bbox is None:
+            pool._store_frame(self, t, now)
+            return
+        from .clips import crop_rects
+
+        pool._store_frame(self, t, now, crop_rects(t.shape[0], t.shape[1], [bbox], pool.pad_ratio)[0])
 
     def add_audio_chunk(self, chunk, sample_rate: int, timestamp: Optional[float] = None) -> None:
         """Mono samples at ``sample_rate`` (the rate of the session's first chunk): resampled once into the audio
@@ -254,7 +270,8 @@ class StreamingSessionPool:
 
     def __init__(self, runner, max_sessions: int, window_seconds: float = 3.0, step_seconds: float = 0.5,
                  max_buffer_seconds: float = 6.0, frames_per_window: int = 8, max_frames: int = 64,
-                 frame_grid: str = "window", frame_stride: Optional[int] = None, max_windows_per_batch: int = 64):
+                 frame_grid: str = "window", frame_stride: Optional[int] = None, max_windows_per_batch: int = 64,
+                 pad_ratio: float = 0.3):
         if runner.device.type != "cuda":
             raise RuntimeError("a streaming session pool runs on the MI355X kernels; build the runner on a GPU device "
                                "(device='cuda')")
@@ -262,7 +279,7 @@ class StreamingSessionPool:
             raise ValueError(f"max_sessions must be at least 1, got {max_sessions}")
         if int(max_windows_per_batch) < 1:
             raise ValueError(f"max_windows_per_batch must be at least 1, got {max_windows_per_batch}")
-        self.runner = runner
+        self.runner, self.pad_ratio = runner, float(pad_ratio)  # pad_ratio: the face crop's (add_frame's bbox)
         self.use_video, self.use_audio = runner.fusion_mode != "audio", runner.fusion_mode != "video"
         self._kw = dict(window_seconds=window_seconds, step_seconds=step_seconds, max_buffer_seconds=max_buffer_seconds,
                         frames_per_window=frames_per_window, max_frames=max_frames, frame_grid=frame_grid,
@@ -308,7 +325,7 @@ class StreamingSessionPool:
         return self._infer(due, now) if due else {}
 
     # ---- device half
-    def _store_frame(self, s: StreamingSession, frame: torch.Tensor, now: float) -> None:
+    def _store_frame(self, s: StreamingSession, frame: torch.Tensor, now: float, rect=None) -> None:
         from . import clips
 
         slot = s.state.add_frame(now)
@@ -317,8 +334,13 @@ class StreamingSessionPool:
             return
         dev = self.runner.device
         frame = frame.to(dev) if frame.is_cuda else clips._h2d(frame.contiguous(), dev)
-        row = self.frame_ring[s.slot * self.max_frames + slot]
-        clips.preprocess_frames(frame[None], self.frame_size, out=row.view(1, 3, self.frame_size, self.frame_size))
+        row = self.frame_ring[s.slot * self.max_frames + slot].view(1, 3, self.frame_size, self.frame_size)
+        if rect is None:
+            clips.preprocess_frames(frame[None], self.frame_size, out=row)
+        else:  # the frame's own padded face box, cropped and resized in one launch
+            H, W, _ = frame.shape
+            clips.crop_resize_frames(frame.contiguous().view(-1), clips.crop_rows([0], H, W, rect[None]),
+                                     self.frame_size, out=row)
 
     def _store_audio(self, s: StreamingSession, flat: torch.Tensor, sr: int) -> None:
         from . import clips

@@ -24,6 +24,9 @@ Rules (all positions are exact rational arithmetic on ``fps``, so a boundary nev
   windows pick identical frames and the frame trunk encodes each once: ``index(w, j) = min(n_frames - 1,
   (f_w // q + j) * q)``.  A window then spans ``(T - 1) * q + 1`` frames from the grid point at or before ``f_w``,
   not exactly its own first to last frame.
+* face boxes (``predict_timeline(face_boxes=...)``, ``checked_face_boxes``): a box belongs to a FRAME, not to a window
+  as in the reference (which detects once per window and reuses that box for its frames), because a frame is shared
+  between windows and encoded once.  One box for the recording, or boxes constant over a window: the two coincide.
 """
 from __future__ import annotations
 
@@ -100,6 +103,27 @@ def window_starts(n_samples: int, sample_rate: int, window_sec, hop_sec, include
     elif include_tail and n_samples - target not in starts:
         starts.append(n_samples - target)
     return starts, target
+
+
+def checked_face_boxes(face_boxes, n_frames: int):
+    """``predict_timeline``'s ``face_boxes`` as a host int64 array: ``None`` stays ``None``, one box ``(x1, y1, x2,
+    y2)`` for the whole recording gives ``[1, 4]``, a table with one raw detector box per decoded frame gives
+    ``[n_frames, 4]`` (an empty row, ``x2 <= x1`` or ``y2 <= y1``: no detection in that frame).  Anything else -- a
+    floating-point array, another shape, a table for another number of frames -- is a ``ValueError``.  Host only."""
+    if face_boxes is None:
+        return None
+    a = face_boxes.detach().cpu().numpy() if isinstance(face_boxes, torch.Tensor) else face_boxes
+    try:
+        a = np.asarray(a)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.dtype.kind not in "iu" or a.shape not in ((4,), (int(n_frames), 4)):
+        raise ValueError(f"face_boxes must be one integer box (x1, y1, x2, y2) or an integer array [{int(n_frames)}, 4]"
+                         f" with one box per decoded frame, got {getattr(a, 'dtype', type(face_boxes))} "
+                         f"{getattr(a, 'shape', '')}")
+    if a.size and int(np.abs(a.astype(np.int64)).max()) >= 2 ** 30:
+        raise ValueError("face_boxes coordinates must be below 2^30")
+    return a.astype(np.int64).reshape(-1, 4)
 
 
 def plan_windows(n_frames: int, fps, n_samples: int, sample_rate: int = 16000, window_sec=3.0, hop_sec=1.0,
