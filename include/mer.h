@@ -448,7 +448,10 @@ int mer_conv_fwd(int N, int H, int W, int C, int K, int R, int S, int stride, in
 
 /* mer_conv_fwd / mer_conv_dgrad with an explicit kernel: -1 auto, 0 the register-staged implicit GEMM,
  * 1 the global_load_lds pipelined one (zero padding served from a zero chunk), 2 the same with 8-wave tiles
- * (the default), 3 with 256-row tiles (8 or 16 waves) on large-M layers. */
+ * (the default), 3 with 256-row tiles (8 or 16 waves) on large-M layers.  The 16-byte epilogue needs K (dgrad: C) a
+ * multiple of 8 and y / dx, stats and every epilogue operand of the dgrad entries below (residual, masks, bn_x, bn_x2,
+ * bn_red, bn_red2) 16-byte aligned; otherwise 0-5 run a scalar epilogue with the same results, and the kernels that
+ * have the 16-byte one only (the halo kernel, the two-K-group tile 7) return hipErrorInvalidValue, nothing written. */
 int mer_conv_fwd_ex(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
                     const void* w_packed, void* y, float* stats, int variant, void* stream);
 
@@ -489,7 +492,10 @@ int mer_conv_dgrad_ds(int N, int H, int W, int C, int K, int R, int S, int strid
  * buffer of such a call needs no zeroing; for an explicit variant it is an upper bound (zero the buffer).  Likewise
  * mer_conv_dgrad_rows for a stride-1 / stride-2 dgrad with variant -1 (one row per BM-row tile, per parity class).   The same geometry test as the launch; a
  * negative hipError_t on invalid arguments.  Pass the count to mer_bn_finalize_rows / mer_partials_sum so the
- * fold reads only written rows (one launch instead of two past 1,024 tile rows). */
+ * fold reads only written rows (one launch instead of two past 1,024 tile rows).  Neither query sees y / dx, stats or
+ * the epilogue operands: both assume them 16-byte aligned.  With one of them misaligned a variant -1 launch takes a
+ * pipelined tile with the scalar epilogue instead of the halo kernel or tile 7 and may write more rows than reported;
+ * use the bound MER_BN_STAT_ROWS(M) - 64 / MER_BN_RED_ROWS(M) - 64 then (as the Python wrappers do). */
 int mer_conv_fwd_rows(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* x,
                       const void* w_packed, int variant);
 int mer_conv_dgrad_rows(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* dy,

@@ -1737,5 +1737,9 @@ MER_API int mer_conv_dgrad_ds(int N, int H, int W, int C, int K, int R, int S, i
   g.bnr_mask = (const bf16_t*)bn_mask; g.bnr_x = (const bf16_t*)bn_x; g.bnr_ms = bn_ms; g.bnr_red = bn_red;
   g.bnr_x2 = (const bf16_t*)bn_x2; g.bnr_ms2 = bn_ms2; g.bnr_red2 = bn_red2;
   g.Wt2 = (const bf16_t*)ds_wt_packed; g.K2 = ds_dy ? ds_K : 0;
+  // dgrad_geom judged the 16-byte epilogue before dx and the epilogue operands were known (mer_conv_dgrad_rows has
+  // none of them): judge it again with them, so a misaligned dx / residual / mask / BN operand / red buffer takes the
+  // scalar epilogue, and the halo and split-K forms, which have the 16-byte one only, refuse it
+  g.vec = conv_vec_ok(g);
   return launch_conv_plan<true>(g, conv_plan(g, true, variant), (hipStream_t)stream);
 }

@@ -574,6 +574,8 @@ def conv_fwd(x, wp, y, stats, R, S, stride, pad, variant=-1):
     _launch("conv_fwd", (N, H, W, C, Kc, R, stride), "mer_conv_fwd_ex", N, H, W, C, Kc, R, S, stride, pad, x.data_ptr(),
             wp.data_ptr(), y.data_ptr(), _ptr(stats), int(variant), stream_ptr())
     if stats is not None:
+        if variant == -1 and _misaligned16(y, stats):  # the rows query cannot see y / stats: take the upper bound
+            return bn_stat_rows(N * Ho * Wo) - 64
         return _partial_rows("mer_conv_fwd_rows", N, H, W, C, Kc, R, S, stride, pad, x.data_ptr(), wp.data_ptr(),
                              int(variant))
     return None
@@ -583,6 +585,13 @@ _ROWS_CACHE = {}
 # Fold only the partial rows a conv wrote (one per persistent workgroup on the halo kernel): the layer1 / stem
 # BatchNorms take the one-launch wide fold.  Same-box step +0.55 % (profiles/r06/step_ab_partial_rows).
 PARTIAL_ROWS = True
+
+
+def _misaligned16(*ts):
+    """Some tensor off a 16-byte boundary: the convolution then runs a pipelined tile with the scalar epilogue where
+    mer_conv_fwd_rows / mer_conv_dgrad_rows, which see neither the output nor the epilogue operands, may assume the
+    halo kernel or the two-K-group tile.  One row per 64 GEMM rows (+ 4 at stride 2) bounds every such launch."""
+    return any(t is not None and t.data_ptr() % 16 for t in ts)
 
 
 def _partial_rows(fn, *args):
@@ -631,6 +640,8 @@ def conv_dgrad(dy, wt, dx, R, S, stride, pad, residual=None, mask=None, variant=
                 int(variant), stream_ptr())
     if bnr is None:
         return None
+    if variant == -1 and _misaligned16(dx, residual, mask, *b):  # the rows query cannot see them: the upper bound
+        return bn_red_rows(N * H * W) - 64
     return _partial_rows("mer_conv_dgrad_rows", N, H, W, C, Kc, R, S, stride, pad, dy.data_ptr(), wt.data_ptr(),
                          ds[0].data_ptr() if ds is not None else 0, int(variant))
 

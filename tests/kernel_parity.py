@@ -696,6 +696,250 @@ def ref_weightnorm_scale(v, g, dt):
     return {"scale": g.to(dt) / torch.sqrt((v * v).sum((0, 1)))}
 
 
+# ---- csrc/conv.hip, csrc/conv_wgrad.hip, csrc/conv_pack.hip: the trunk convolutions (NHWC bf16, fp32 accumulate) ----
+def conv_out(n, R, stride, pad):
+    return (n + 2 * pad - R) // stride + 1
+
+
+def ref_conv_fwd(x, w, stride, pad, dt, tap_scale=None, shift=0):
+    """y[n, oh, ow, k] = sum_{r, s, c} x[n, oh st - pad + r, ow st - pad + s, c] w[k, c, r, s] (include/mer.h) as a
+    direct sum over taps on an explicitly zero-padded x: one shifted strided slice and one matmul per tap, taps in
+    (r, s) order.  x [N, H, W, C], w [K, C, R, S] (the bf16 rounding of the fp32 weight: what the pack stores).
+    ``tap_scale(r, s)`` (None, or a tensor broadcastable to [N, Ho, Wo, 1] the tap's term is multiplied by) and
+    ``shift`` (the frame placed ``shift`` pixels off its place inside the padding) exist for the CPU mutation
+    checks only."""
+    N, H, W, C = x.shape
+    Kc, _, R, S = w.shape
+    Ho, Wo = conv_out(H, R, stride, pad), conv_out(W, S, stride, pad)
+    xp = torch.zeros(N, H + 2 * pad + 2, W + 2 * pad + 2, C, dtype=dt)  # one spare pixel around the padding
+    xp[:, pad + 1 + shift:pad + 1 + shift + H, pad + 1 + shift:pad + 1 + shift + W] = x.to(dt)
+    w = w.to(dt)
+    y = torch.zeros(N, Ho, Wo, Kc, dtype=dt)
+    for r in range(R):
+        for s in range(S):
+            v = xp[:, r + 1:r + 1 + stride * (Ho - 1) + 1:stride, s + 1:s + 1 + stride * (Wo - 1) + 1:stride]
+            term = v @ w[:, :, r, s].t()
+            sc = tap_scale(r, s) if tap_scale is not None else None
+            y = y + (term if sc is None else term * sc.to(dt))
+    return {"y": y}
+
+
+def ref_conv_dgrad(dy, w, H, W, stride, pad, dt, residual=None, mask=None, ds=None, mask_ge=False):
+    """dx[n, h, w, c] = sum_{r, s, k} dy[n, (h + pad - r) / st, (w + pad - s) / st, k] w[k, c, r, s]: a scatter per tap
+    into a zero-padded dx, then the crop.  ``ds`` = (ds_dy [N, Ho, Wo, Kd], wd [Kd, C, 1, 1]): the input gradient of a
+    1x1 / stride-2 / pad-0 downsample of the same input, into pixels (2i, 2j) of the same accumulator before any
+    rounding.  Then + residual: everywhere when ``mask`` is None, else only where mask > 0 (+0.0, -0.0 and negative
+    values add nothing).  ``mask_ge``: mask >= 0 instead (the CPU mutation check only)."""
+    N, Ho, Wo, Kc = dy.shape
+    _, C, R, S = w.shape
+    assert (Ho, Wo) == (conv_out(H, R, stride, pad), conv_out(W, S, stride, pad))
+    dxp = torch.zeros(N, H + 2 * pad, W + 2 * pad, C, dtype=dt)
+    dy, w = dy.to(dt), w.to(dt)
+    for r in range(R):
+        for s in range(S):
+            dxp[:, r:r + stride * (Ho - 1) + 1:stride, s:s + stride * (Wo - 1) + 1:stride] += dy @ w[:, :, r, s]
+    if ds is not None:
+        ds_dy, wd = ds
+        assert tuple(ds_dy.shape[:3]) == (N, Ho, Wo) and stride == 2
+        dxp[:, pad:pad + 2 * (Ho - 1) + 1:2, pad:pad + 2 * (Wo - 1) + 1:2] += ds_dy.to(dt) @ wd.to(dt)[:, :, 0, 0]
+    dx = dxp[:, pad:pad + H, pad:pad + W].contiguous()
+    if residual is not None:
+        res = residual.to(dt)
+        if mask is not None:
+            res = torch.where((mask >= 0) if mask_ge else (mask > 0), res, torch.zeros((), dtype=dt))
+        dx = dx + res
+    return {"dx": dx}
+
+
+def wgrad_split_pixels(P, splits):
+    """Pixels per split of conv_wgrad.hip's plan: ceil(P / splits) rounded up to whole 64-pixel granules."""
+    return ((P + splits - 1) // splits + 63) // 64 * 64
+
+
+def ref_conv_wgrad(x, dy, R, S, stride, pad, creal, dw0, dt, splits=1, chunk=32, c0=0, drop_tail=False):
+    """dw0 + dw[k, c, r, s], dw = sum_p dy[p, k] x(p; r, s, c) for c < creal, in the order conv_wgrad.hip documents:
+    every split (whole 64-pixel granules, wgrad_split_pixels) accumulated sequentially in ``chunk``-pixel pieces (one
+    MFMA covers 32 pixels), the splits added in order, the total added to dw0.  In float64 the grouping changes
+    nothing; in float32 it makes the bar grow with the chain length the way any fp32 chain does.  ``c0`` (the creal
+    channels read from channel c0 on) and ``drop_tail`` (the last, partial granule of every split dropped) exist for
+    the CPU mutation checks only."""
+    N, H, W, C = x.shape
+    _, Ho, Wo, Kc = dy.shape
+    assert (Ho, Wo) == (conv_out(H, R, stride, pad), conv_out(W, S, stride, pad))
+    xp = torch.zeros(N, H + 2 * pad, W + 2 * pad, C, dtype=dt)
+    xp[:, pad:pad + H, pad:pad + W] = x.to(dt)
+    P = N * Ho * Wo
+    cols = [xp[:, r:r + stride * (Ho - 1) + 1:stride, s:s + stride * (Wo - 1) + 1:stride, c0:c0 + creal]
+            .reshape(P, creal) for r in range(R) for s in range(S)]
+    a = torch.stack(cols, 1).reshape(P, R * S * creal)  # [P][(r, s)][c]
+    dyt = dy.to(dt).reshape(P, Kc).t().contiguous()
+    per = wgrad_split_pixels(P, splits)
+    total = None
+    for beg in range(0, P, per):
+        end = min(P, beg + per)
+        if drop_tail and (end - beg) % 64:
+            end -= (end - beg) % 64
+        acc = torch.zeros(Kc, R * S * creal, dtype=dt)
+        for p0 in range(beg, end, chunk):
+            p1 = min(end, p0 + chunk)
+            acc = acc + dyt[:, p0:p1] @ a[p0:p1]
+        total = acc if total is None else total + acc
+    dw = total.reshape(Kc, R, S, creal).permute(0, 3, 1, 2)
+    return {"dw": dw0.to(dt) + dw}
+
+
+def ref_conv_sums(y_stored, dt):
+    """Forward BatchNorm statistics as include/mer.h defines them: per channel (sum, sum of squares) of the STORED
+    bf16 outputs (the kernel's own y, widened) -> [C, 2]."""
+    y = y_stored.to(dt).reshape(-1, y_stored.shape[-1])
+    return {"stats": torch.stack([y.sum(0), (y * y).sum(0)], -1)}
+
+
+def ref_bnr_sums(dx_stored, mask, x, ms, dt):
+    """The dgrad's fused BN-backward sums (mer_conv_dgrad_bnr): g = the STORED bf16 dx where mask > 0, else 0;
+    (sum g, sum g (x - mean) rstd) per channel with (mean, rstd) = ms[c] -> [C, 2]."""
+    C = dx_stored.shape[-1]
+    dx, x, ms = dx_stored.to(dt).reshape(-1, C), x.to(dt).reshape(-1, C), ms.to(dt)
+    g = torch.where(mask.reshape(-1, C) > 0, dx, torch.zeros((), dtype=dt))
+    return {"red": torch.stack([g.sum(0), (g * (x - ms[:, 0]) * ms[:, 1]).sum(0)], -1)}
+
+
+def ref_pack_conv_weight(w, cp, mode):
+    """The exact bf16 tensor of each weight layout of csrc/conv_pack.hip from the fp32 weight [K, C, R, S]:
+    mode 0 [K][R][S][Cp]; mode 1 (and 3, the same values) [Cp][R][S][K]; mode 2 the space-to-depth stem layout
+    [K][(R+2)/2][(S+2)/2][Cp] with out[k, ry, rx, (dy 2 + dx) C + c] = w[k, c, 2 ry + dy - 1, 2 rx + dx - 1] (zero
+    where that tap is outside the filter).  Channels >= C (mode 2: >= 4 C) are zero."""
+    Kc, C, R, S = w.shape
+    wb = to_bf16(w)
+    if mode == 0:
+        out = torch.zeros(Kc, R, S, cp, dtype=BF16)
+        out[..., :C] = wb.permute(0, 2, 3, 1)
+    elif mode in (1, 3):
+        out = torch.zeros(cp, R, S, Kc, dtype=BF16)
+        out[:C] = wb.permute(1, 2, 3, 0)
+    else:
+        Ro, So = (R + 2) // 2, (S + 2) // 2
+        out = torch.zeros(Kc, Ro, So, cp, dtype=BF16)
+        for ry in range(Ro):
+            for rx in range(So):
+                for d in range(4):
+                    r, s = 2 * ry + (d >> 1) - 1, 2 * rx + (d & 1) - 1
+                    if 0 <= r < R and 0 <= s < S:
+                        out[:, ry, rx, d * C:(d + 1) * C] = wb[:, :, r, s]
+    return out
+
+
+def ref_pack_input_s2d(x):
+    """fp32 NCHW frames [N, C <= 4, H, W] (H, W even) -> the exact bf16 [N][H/2+3][W/2+3][16] of mer_pack_input_s2d:
+    pixel (j, i) holds the 2x2 block (j - 2, i - 2) of the frame, channel (dy 2 + dx) C + c; two leading and one
+    trailing border rows / columns and the channels >= 4 C are zero."""
+    N, C, H, W = x.shape
+    out = torch.zeros(N, H // 2 + 3, W // 2 + 3, 16, dtype=BF16)
+    xb = to_bf16(x)
+    for d in range(4):
+        out[:, 2:2 + H // 2, 2:2 + W // 2, d * C:(d + 1) * C] = xb[:, :, (d >> 1)::2, (d & 1)::2].permute(0, 2, 3, 1)
+    return out
+
+
+SUBNORMAL_BF16 = float(torch.tensor([1], dtype=torch.int16).view(BF16)[0])  # 2^-133: the smallest positive bf16
+
+
+def conv_inputs(N, H, W, C, Kc, R, stride, pad, seed=None, ds_k=0):
+    """Seeded inputs of one convolution shape, all bf16-valued float32 CPU tensors but the fp32 weight ``w32`` (the
+    packs round it; ``w`` is that rounding): unit-normal x / dy / residual / BN inputs, weights scaled by
+    1 / sqrt(R S C), a unit-normal mask whose first elements are +0.0, -0.0, a negative value and the smallest
+    positive bf16, BatchNorm (mean, rstd) pairs, and with ``ds_k`` the fused downsample's dy and weight."""
+    if seed is None:  # a polynomial of the shape: the same inputs under every interpreter
+        seed = 0
+        for v in (N, H, W, C, Kc, R, stride, pad):
+            seed = (seed * 1009 + v) % 2147483647
+    g = gen(seed)
+    Ho, Wo = conv_out(H, R, stride, pad), conv_out(W, R, stride, pad)
+    w32 = randn(g, Kc, C, R, R) / math.sqrt(R * R * C)
+    i = {"x": bf16_values(g, N, H, W, C), "w32": w32, "w": to_bf16(w32).to(F32), "dy": bf16_values(g, N, Ho, Wo, Kc),
+         "res": bf16_values(g, N, H, W, C), "mask": bf16_values(g, N, H, W, C), "xb": bf16_values(g, N, H, W, C),
+         "xb2": bf16_values(g, N, H, W, C),
+         "ms": torch.stack([randn(g, C), torch.rand(C, generator=g) + 0.5], 1).contiguous(),
+         "ms2": torch.stack([randn(g, C), torch.rand(C, generator=g) + 0.5], 1).contiguous()}
+    flat = i["mask"].reshape(-1)
+    for j, v in enumerate((0.0, -0.0, -1.0, SUBNORMAL_BF16)):
+        flat[j * 3 % flat.numel()] = v
+    if ds_k:
+        wd32 = randn(g, ds_k, C, 1, 1) / math.sqrt(C)
+        i.update(ds_dy=bf16_values(g, N, Ho, Wo, ds_k), wd32=wd32, wd=to_bf16(wd32).to(F32))
+    return i
+
+
+# Every (N, H, W, C, Kc, R, stride, pad) tests/test_conv_kernels_gpu.py runs forward and as an input gradient
+# (dx [N, H, W, C] from dy [N, Ho, Wo, Kc]); tests/test_kernel_parity_cpu.py shows the restatements leave at least 90 %
+# of every one of their bf16 outputs determined.  What each shape is there for is said at the GPU test's case lists.
+CONV_SHAPES = [
+    (2, 7, 7, 64, 64, 3, 1, 1), (3, 9, 9, 128, 192, 3, 1, 1), (2, 9, 9, 64, 128, 3, 2, 1), (2, 8, 8, 64, 128, 1, 2, 0),
+    (2, 12, 12, 64, 64, 3, 1, 1), (3, 17, 17, 16, 24, 3, 1, 1), (2, 30, 30, 8, 64, 7, 2, 3),
+    (2, 6, 9, 64, 64, 3, 1, 1), (2, 9, 6, 64, 128, 3, 2, 1), (1, 5, 13, 64, 64, 3, 1, 1), (2, 7, 7, 64, 136, 3, 1, 1),
+    (2, 7, 7, 136, 64, 3, 1, 1), (5, 3, 28, 64, 64, 3, 1, 1), (300, 3, 28, 64, 64, 3, 1, 1),
+    (800, 3, 28, 64, 64, 3, 1, 1), (2, 8, 8, 256, 64, 1, 1, 0), (2, 8, 8, 128, 256, 3, 2, 1),
+    (1, 7, 7, 64, 64, 3, 3, 1)]
+CONV_FWD_ONLY = [(2, 7, 7, 64, 20, 3, 1, 1), (4, 56, 56, 64, 512, 3, 1, 1)]
+CONV_DGRAD_ONLY = [(4, 56, 56, 512, 64, 3, 1, 1), (4, 56, 56, 512, 64, 3, 2, 1), (1, 12, 12, 8, 64, 11, 2, 5)]
+CONV_FORMS = ("plain", "res", "res_mask", "ds")
+
+
+class ConvCase:
+    """The seeded inputs of one shape and its restated outputs (float64, float32), each computed once on demand and
+    then shared: "fwd", and the input-gradient forms "plain", "res" (+ residual), "res_mask" (+ residual where
+    mask > 0) and "ds" ("res_mask" with the fused 1x1 / stride-2 downsample gradient; 3x3 / stride-2 / pad-1 shapes
+    with Kc a multiple of 64 only)."""
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+        N, H, W, C, Kc, R, stride, pad = self.shape
+        self.has_ds = R == 3 and stride == 2 and pad == 1 and Kc % 64 == 0
+        self.i = conv_inputs(*self.shape, ds_k=64 if self.has_ds else 0)
+        self._refs = {}
+
+    def ref(self, form):
+        if form not in self._refs:
+            N, H, W, C, Kc, R, stride, pad = self.shape
+            i = self.i
+
+            def run(dt):
+                if form == "fwd":
+                    return ref_conv_fwd(i["x"], i["w"], stride, pad, dt)["y"]
+                res = None if form == "plain" else i["res"]
+                mask = i["mask"] if form in ("res_mask", "ds") else None
+                ds = (i["ds_dy"], i["wd"]) if form == "ds" else None
+                return ref_conv_dgrad(i["dy"], i["w"], H, W, stride, pad, dt, res, mask, ds)["dx"]
+            self._refs[form] = (run(F64), run(F32))
+        return self._refs[form]
+
+
+_CONV_CASES = {}
+
+
+def conv_case(shape) -> ConvCase:
+    shape = tuple(shape)
+    if shape not in _CONV_CASES:
+        _CONV_CASES[shape] = ConvCase(shape)
+    return _CONV_CASES[shape]
+
+
+def stem_case(N=3, Hf=112, Kc=64, seed=20261206):
+    """The stem off its benchmark batch: fp32 frames [N, 3, Hf, Hf], the 7x7 weight, and the restated output of the
+    original 7x7 / stride-2 / pad-3 convolution of the bf16-rounded frames -- what mer_pack_input_s2d, the mode-2
+    weight pack and the 4x4 / stride-1 / pad-0 convolution of their outputs must reproduce."""
+    key = ("stem", N, Hf, Kc, seed)
+    if key not in _CONV_CASES:
+        g = gen(seed)
+        frames = randn(g, N, 3, Hf, Hf)
+        w32 = randn(g, Kc, 3, 7, 7) / math.sqrt(147.0)
+        x = to_bf16(frames).to(F32).permute(0, 2, 3, 1).contiguous()
+        w = to_bf16(w32).to(F32)
+        _CONV_CASES[key] = {"frames": frames, "w32": w32, "x": x, "w": w, "dy": bf16_values(g, N, Hf // 2, Hf // 2, Kc),
+                            "ref": tuple(ref_conv_fwd(x, w, 2, 3, dt)["y"] for dt in (F64, F32))}
+    return _CONV_CASES[key]
+
+
 # ======================================================================================================
 # One small seeded instance of every restatement (tests/test_kernel_parity_cpu.py checks that its float32
 # evaluation is a non-degenerate bar).  name -> fn(dt) -> dict of outputs.
@@ -796,6 +1040,7 @@ def _instances():
     pr, o0 = randn(gb, 65, 40), randn(gb, 40)
     inst["rows_sum"] = lambda dt: ref_rows_sum(pr, o0, dt)
     inst.update(_audio_instances())
+    inst.update(_conv_instances())
     return inst
 
 
@@ -866,16 +1111,45 @@ def _audio_instances():
     return inst
 
 
+def _conv_instances():
+    """csrc/conv.hip, conv_wgrad.hip, conv_pack.hip: one small instance per restatement."""
+    inst = {}
+    N, H, W, C, Kc = 2, 6, 9, 64, 64
+    i = conv_inputs(N, H, W, C, Kc, 3, 1, 1, seed=20261201)
+    inst["conv_fwd"] = lambda dt: ref_conv_fwd(i["x"], i["w"], 1, 1, dt)
+    inst["conv_dgrad"] = lambda dt: ref_conv_dgrad(i["dy"], i["w"], H, W, 1, 1, dt)
+    inst["conv_dgrad_res_mask"] = lambda dt: ref_conv_dgrad(i["dy"], i["w"], H, W, 1, 1, dt, i["res"], i["mask"])
+    s = conv_inputs(N, 9, 6, C, 128, 3, 2, 1, seed=20261202, ds_k=64)
+    inst["conv_fwd_s2"] = lambda dt: ref_conv_fwd(s["x"], s["w"], 2, 1, dt)
+    inst["conv_dgrad_s2_ds"] = lambda dt: ref_conv_dgrad(s["dy"], s["w"], 9, 6, 2, 1, dt, s["res"], s["mask"],
+                                                         ds=(s["ds_dy"], s["wd"]))
+    dw0 = randn(gen(20261203), Kc, C, 3, 3)
+    inst["conv_wgrad"] = lambda dt: ref_conv_wgrad(i["x"], i["dy"], 3, 3, 1, 1, C, dw0, dt, splits=2)
+    stored = to_bf16(ref_conv_fwd(i["x"], i["w"], 1, 1, F64)["y"]).to(F32)
+    inst["conv_sums"] = lambda dt: ref_conv_sums(stored, dt)
+    inst["conv_bnr_sums"] = lambda dt: ref_bnr_sums(stored, i["mask"], i["xb"], i["ms"], dt)
+    w7 = randn(gen(20261204), 8, 3, 7, 7)
+    for mode in (0, 1, 2):
+        inst[f"conv_pack_w{mode}"] = lambda dt, mode=mode: {"out": ref_pack_conv_weight(w7, 16 if mode == 2 else 8,
+                                                                                     mode).to(dt)}
+    frames = randn(gen(20261205), 2, 3, 6, 10)
+    inst["conv_pack_s2d"] = lambda dt: {"out": ref_pack_input_s2d(frames).to(dt)}
+    return inst
+
+
 INSTANCES = _instances()
 # Outputs that are copies of an input in any precision (no arithmetic): their bar is zero by construction and only
 # the one-ulp floor of assert_fp64_parity applies.  Without a residual the saved pre-norm sum is x itself; the max
 # pool's y and argmax and the eval-mode BatchNorm mean are copies; the max pool's dx adds at most four bf16 values of
 # one scale, which float32 does exactly.
-EXACT_OUTPUTS = {"add_ln_no_r": {"s"}, "maxpool": {"y", "arg", "dx"}, "bn_finalize_eval": {"mean"}}
+EXACT_OUTPUTS = {"add_ln_no_r": {"s"}, "maxpool": {"y", "arg", "dx"}, "bn_finalize_eval": {"mean"},
+                 "conv_pack_w0": {"out"}, "conv_pack_w1": {"out"}, "conv_pack_w2": {"out"}, "conv_pack_s2d": {"out"}}
 # Outputs the kernels store as bfloat16: judged by assert_bf16_parity.
 BF16_OUTPUTS = {"bn_apply": {"y"}, "bn_apply_res_relu": {"y"}, "bn_apply_resbn_relu": {"y"}, "bn_bwd": {"dx"},
                 "bn_bwd_running": {"dx"}, "maxpool": {"y", "dx"}, "avgpool": {"dx"},
                 "gemm_bf16_none": {"out"}, "gemm_bf16_relu": {"out"}, "gemm_bf16_gelu": {"out"},
                 "gemm_bf16_gelu_plain": {"out"}, "gemm_bf16_gelu_drop": {"out"}, "gemm_bf16_rows": {"out"},
                 "posconv_gelu": {"out"}, "posconv_none": {"out"}, "layernorm": {"y"}, "layernorm_drop": {"y"},
-                "ln_bwd": {"dx"}, "gelu": {"f"}, "gelu_bwd": {"dz"}, "dropout_rows": {"y"}}
+                "ln_bwd": {"dx"}, "gelu": {"f"}, "gelu_bwd": {"dz"}, "dropout_rows": {"y"},
+                "conv_fwd": {"y"}, "conv_fwd_s2": {"y"}, "conv_dgrad": {"dx"}, "conv_dgrad_res_mask": {"dx"},
+                "conv_dgrad_s2_ds": {"dx"}}

@@ -6,7 +6,12 @@ restatement takes the first maximum; csrc/common.h ``fdiv``, emulated in float32
 at 2^23 + 7 for a divisor of 8.  For the bf16 GEMM and the WavLM row kernels (tests/test_gemm_bf16_parity_gpu.py,
 tests/test_wavlm_rows_kernels_gpu.py) the faults a loose bar would let through are applied to the float32 restatement
 and must be rejected: a dropped K chunk, swapped bias columns, the residual before the activation, dropout after the
-residual, a truncating bf16 store, a shifted tap, an ``ln_bwd`` partial row over the wrong rows."""
+residual, a truncating bf16 store, a shifted tap, an ``ln_bwd`` partial row over the wrong rows.  For the trunk
+convolutions (tests/test_conv_kernels_gpu.py): the tap-sum restatements are torch's convolutions in float64, leave at
+least 90 % of every bf16 output determined at every shape and form the GPU file runs, and the faults a relative-RMS bar
+lets through are rejected -- a tap dropped at the border only, padding off by one pixel, ``mask >= 0`` at planted signed
+zeros, the downsample gradient rounded before the add, a dropped K chunk of one tile, a truncating store, sums over
+unrounded values, wgrad channels from the wrong offset, a dropped partial granule."""
 import numpy as np
 import pytest
 import torch
@@ -362,3 +367,212 @@ def test_fdiv_is_exact_below_2_22_and_first_wrong_at_2_23_plus_7_for_8():
     assert np.array_equal(fdiv_emulated(wrong8, 8), wrong8 // 8 + 1)  # ... gives q + 1
     for d in (3, 7, 28, 56, 112):
         assert 1.4 * (1 << 22) < first[d] < 1.6 * (1 << 22), (d, first[d])
+
+
+# ---- csrc/conv.hip / conv_wgrad.hip / conv_pack.hip: the restatements of tests/test_conv_kernels_gpu.py ----
+def _conv_forms(shape):
+    c = kp.conv_case(shape)
+    forms = [] if shape in kp.CONV_DGRAD_ONLY else ["fwd"]
+    if shape not in kp.CONV_FWD_ONLY:
+        forms += [f for f in kp.CONV_FORMS if f != "ds" or c.has_ds]
+    return c, forms
+
+
+@pytest.mark.parametrize("shape", kp.CONV_SHAPES + kp.CONV_FWD_ONLY + kp.CONV_DGRAD_ONLY, ids=str)
+def test_conv_restatements_leave_every_gpu_shape_determined(shape):
+    """min_determined = 0.9 is a condition on the inputs: the restatement alone meets it for every shape and form the
+    GPU test runs (assert_bf16_parity asserts the share), with a bar far below one bf16 step."""
+    c, forms = _conv_forms(shape)
+    for f in forms:
+        ref64, ref32 = c.ref(f)
+        kp.assert_bf16_parity(kp.to_bf16(ref32), ref64, ref32, what=f"{shape} {f}")
+        assert kp.bf16_interval(ref64, ref32)[2] <= 1e-5 * float(ref64.abs().max())
+
+
+def test_stem_restatement_is_determined_and_the_s2d_form_is_the_7x7_conv():
+    """The 4x4 / stride-1 / pad-0 convolution of the restated space-to-depth packs IS the 7x7 / stride-2 / pad-3 one
+    (float64, a small frame), so the GPU test may judge the stem kernel against the latter."""
+    s = kp.stem_case()
+    kp.assert_bf16_parity(kp.to_bf16(s["ref"][1]), s["ref"][0], s["ref"][1], what="stem")
+    g = kp.gen(31)
+    frames, w32 = kp.randn(g, 2, 3, 10, 14), kp.randn(g, 8, 3, 7, 7)
+    xs, ws = kp.ref_pack_input_s2d(frames).float(), kp.ref_pack_conv_weight(w32, 16, 2).float()
+    assert tuple(xs.shape) == (2, 8, 10, 16) and tuple(ws.shape) == (8, 4, 4, 16)
+    a = kp.ref_conv_fwd(xs, ws.permute(0, 3, 1, 2), 1, 0, kp.F64)["y"]
+    b = kp.ref_conv_fwd(kp.to_bf16(frames).float().permute(0, 2, 3, 1), kp.to_bf16(w32).float(), 2, 3, kp.F64)["y"]
+    assert tuple(a.shape) == tuple(b.shape) == (2, 5, 7, 8) and float((a - b).abs().max()) < 1e-12
+    # every border slot and pad channel of both packs is zero
+    assert float(xs[:, :2].abs().max()) == 0 and float(xs[:, -1].abs().max()) == 0
+    assert float(xs[..., 12:].abs().max()) == 0
+    assert float(xs[:, :, :2].abs().max()) == 0 and float(xs[:, :, -1].abs().max()) == 0
+    assert float(ws[..., 12:].abs().max()) == 0 and float(ws[:, 0, :, :6].abs().max()) == 0  # tap r = -1: dy = 0 rows
+
+
+def test_conv_restatements_are_the_library_convolutions():
+    """The tap sums against torch's own convolutions in float64 (a check of the restatement's text, not a bar)."""
+    F = torch.nn.functional
+    for shape in [(2, 6, 9, 64, 64, 3, 1, 1), (2, 9, 6, 64, 128, 3, 2, 1), (2, 30, 30, 8, 64, 7, 2, 3),
+                  (1, 7, 7, 64, 64, 3, 3, 1), (2, 8, 8, 64, 128, 1, 2, 0)]:
+        N, H, W, C, Kc, R, stride, pad = shape
+        c = kp.conv_case(shape)
+        i = c.i
+        x, w, dy = (i[k].double() for k in ("x", "w", "dy"))
+        xn = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+        wn = w.clone().requires_grad_(True)
+        y = F.conv2d(xn, wn, stride=stride, padding=pad)
+        assert float((y.detach().permute(0, 2, 3, 1) - c.ref("fwd")[0]).abs().max()) < 1e-12
+        gx, gw = torch.autograd.grad(y, [xn, wn], dy.permute(0, 3, 1, 2))
+        assert float((gx.permute(0, 2, 3, 1) - c.ref("plain")[0]).abs().max()) < 1e-12
+        dw0 = kp.randn(kp.gen(5), Kc, C, R, R)
+        for splits in (1, 3):
+            dw = kp.ref_conv_wgrad(i["x"], i["dy"], R, R, stride, pad, C, dw0, kp.F64, splits=splits)["dw"]
+            assert float((dw - dw0.double() - gw).abs().max()) < 1e-11
+        if c.has_ds:
+            yd = F.conv2d(xn, i["wd"].double(), stride=2)
+            gd, = torch.autograd.grad(yd, [xn], i["ds_dy"].double().permute(0, 3, 1, 2))
+            keep = (i["mask"] > 0).double()
+            want = (gx + gd).permute(0, 2, 3, 1) + i["res"].double() * keep
+            assert float((want - c.ref("ds")[0]).abs().max()) < 1e-12
+
+
+def test_conv_mask_restatement_at_signed_zeros_and_the_smallest_bf16():
+    i = kp.conv_case((2, 7, 7, 64, 64, 3, 1, 1)).i
+    m = i["mask"].reshape(-1)
+    assert m[0] == 0 and not bool(torch.signbit(m[0])) and m[3] == 0 and bool(torch.signbit(m[3]))
+    assert m[6] == -1 and 0 < float(m[9]) == kp.SUBNORMAL_BF16 == 2.0 ** -133
+    assert float(kp.to_bf16(m[9:10]).float()) == kp.SUBNORMAL_BF16  # bf16-representable
+    plain, masked = (kp.conv_case((2, 7, 7, 64, 64, 3, 1, 1)).ref(f)[0].reshape(-1) for f in ("plain", "res_mask"))
+    r = i["res"].double().reshape(-1)
+    assert bool((masked[[0, 3, 6]] == plain[[0, 3, 6]]).all()) and float(masked[9]) == float(plain[9] + r[9])
+
+
+CONV_MUT = (2, 6, 9, 64, 64, 3, 1, 1)
+
+
+def test_conv_fwd_mutations_are_rejected():
+    N, H, W, C, Kc, R, stride, pad = CONV_MUT
+    c = kp.conv_case(CONV_MUT)
+    i = c.i
+    ref64, ref32 = c.ref("fwd")
+    kp.assert_bf16_parity(kp.to_bf16(ref32), ref64, ref32, what="unmutated")
+    # one tap dropped at the image border only: the centre tap of the first output row (it reads real pixels there)
+    border = torch.ones(1, H, W, 1)
+    border[:, 0] = 0
+    bad = kp.ref_conv_fwd(i["x"], i["w"], stride, pad, kp.F32,
+                          tap_scale=lambda r, s: border if (r, s) == (1, 1) else None)
+    assert bool((bad["y"][:, 1:] == ref32[:, 1:]).all())
+    _rejected_both_ways(bad["y"], ref64, ref32, "border tap")
+    # ... and a corner tap at the one pixel column where it is inside the frame's last column
+    col = torch.ones(1, H, W, 1)
+    col[:, :, W - 2] = 0
+    bad = kp.ref_conv_fwd(i["x"], i["w"], stride, pad, kp.F32, tap_scale=lambda r, s: col if (r, s) == (2, 2) else None)
+    _rejected_both_ways(bad["y"], ref64, ref32, "last-column tap")
+    # padding off by one pixel
+    for shift in (1, -1):
+        _rejected_both_ways(kp.ref_conv_fwd(i["x"], i["w"], stride, pad, kp.F32, shift=shift)["y"], ref64, ref32, "pad")
+    # the last 64-deep K chunk (tap (2, 2), channels C - 64 ...) of the second 64-row tile dropped
+    xp = torch.zeros(N, H + 2, W + 2, C)
+    xp[:, 1:H + 1, 1:W + 1] = i["x"]
+    last = (xp[:, 2:2 + H, 2:2 + W, C - 64:] @ i["w"][:, C - 64:, 2, 2].t()).reshape(-1, Kc)
+    bad = ref32.clone().reshape(-1, Kc)
+    bad[64:128] -= last[64:128]
+    _rejected_both_ways(bad.reshape(ref32.shape), ref64, ref32, "K chunk of one tile")
+    # a truncating bf16 store
+    with pytest.raises(AssertionError, match="outside the bf16 interval"):
+        kp.assert_bf16_parity(kp.bf16_truncate(ref32), ref64, ref32, what="truncating store")
+    # the statistics taken over the unrounded values instead of the stored ones
+    stored = kp.to_bf16(ref32).float()
+    s64, s32 = (kp.ref_conv_sums(stored, dt)["stats"] for dt in (kp.F64, kp.F32))
+    kp.assert_fp64_parity(s32, s64, s32, what="stats of the stored values")
+    with pytest.raises(AssertionError):
+        kp.assert_fp64_parity(kp.ref_conv_sums(ref32, kp.F32)["stats"], s64, s32, what="stats of the accumulators")
+    for q in range(2):  # either column alone
+        with pytest.raises(AssertionError):
+            kp.assert_fp64_parity(kp.ref_conv_sums(ref32, kp.F32)["stats"][:, q], s64[:, q], s32[:, q], what="stats")
+
+
+@pytest.mark.parametrize("shape", [CONV_MUT, (2, 9, 6, 64, 128, 3, 2, 1)], ids=str)
+def test_conv_dgrad_mutations_are_rejected(shape):
+    N, H, W, C, Kc, R, stride, pad = shape
+    c = kp.conv_case(shape)
+    i = c.i
+    form = "ds" if c.has_ds else "res_mask"
+    ds = (i["ds_dy"], i["wd"]) if c.has_ds else None
+    ref64, ref32 = c.ref(form)
+    kp.assert_bf16_parity(kp.to_bf16(ref32), ref64, ref32, what="unmutated")
+    # mask >= 0 instead of mask > 0: the planted +0.0 and -0.0 then receive the residual
+    bad = kp.ref_conv_dgrad(i["dy"], i["w"], H, W, stride, pad, kp.F32, i["res"], i["mask"], ds, mask_ge=True)["dx"]
+    diff = (bad != ref32).reshape(-1).nonzero().reshape(-1).tolist()
+    assert diff == [0, 3], diff  # exactly the two zeros (the mask has no other)
+    _rejected_both_ways(bad, ref64, ref32, "mask >= 0")
+    # the mask ignored / the masked elements given the residual's negative
+    _rejected_both_ways(c.ref("res")[1] if not c.has_ds else kp.ref_conv_dgrad(
+        i["dy"], i["w"], H, W, stride, pad, kp.F32, i["res"], None, ds)["dx"], ref64, ref32, "no mask")
+    # a truncating store
+    with pytest.raises(AssertionError, match="outside the bf16 interval"):
+        kp.assert_bf16_parity(kp.bf16_truncate(ref32), ref64, ref32, what="truncating store")
+    # one tap of one border row dropped: tap (1, 1) at input row 0 (stride 1: it reads dy row 0; stride 2 likewise)
+    w2 = i["w"].clone()
+    w2[:, :, 1, 1] = 0
+    drop = kp.ref_conv_dgrad(i["dy"], w2, H, W, stride, pad, kp.F32, i["res"], i["mask"], ds)["dx"]
+    bad = ref32.clone()
+    bad[:, 0] = drop[:, 0]
+    _rejected_both_ways(bad, ref64, ref32, "border tap")
+    # the BN-backward sums over the unrounded gradient, and under mask >= 0
+    stored = kp.to_bf16(ref32).float()
+    r64, r32 = (kp.ref_bnr_sums(stored, i["mask"], i["xb"], i["ms"], dt)["red"] for dt in (kp.F64, kp.F32))
+    kp.assert_fp64_parity(r32, r64, r32, what="sums of the stored gradient")
+    with pytest.raises(AssertionError):
+        kp.assert_fp64_parity(kp.ref_bnr_sums(ref32, i["mask"], i["xb"], i["ms"], kp.F32)["red"], r64, r32,
+                              what="unrounded")
+    ge = torch.where(i["mask"] == 0, torch.ones(()), i["mask"])
+    with pytest.raises(AssertionError):
+        kp.assert_fp64_parity(kp.ref_bnr_sums(stored, ge, i["xb"], i["ms"], kp.F32)["red"], r64, r32, what="mask >= 0")
+    if c.has_ds:
+        # the two-launch form: the downsample's gradient rounded to bf16 before the 3x3 gradient is added to it
+        dsg = kp.ref_conv_dgrad(i["ds_dy"], i["wd"], H, W, 2, 0, kp.F32)["dx"]
+        keep = i["mask"] > 0
+        two = kp.ref_conv_dgrad(i["dy"], i["w"], H, W, stride, pad, kp.F32)["dx"] + kp.to_bf16(dsg).float() + \
+            torch.where(keep, i["res"], torch.zeros(()))
+        _rejected_both_ways(two, ref64, ref32, "downsample gradient rounded before the add")
+
+
+def test_conv_wgrad_mutations_are_rejected():
+    shape = (2, 30, 30, 8, 64, 7, 2, 3)  # P = 450 pixels: 7 granules and a partial one
+    N, H, W, C, Kc, R, stride, pad = shape
+    i = kp.conv_case(shape).i
+    dw0 = kp.randn(kp.gen(8), Kc, 3, R, R)
+    args = (i["x"], i["dy"], R, R, stride, pad, 3, dw0)
+    ref64, ref32 = (kp.ref_conv_wgrad(*args, dt, splits=2)["dw"] for dt in (kp.F64, kp.F32))
+    assert kp.wgrad_split_pixels(450, 2) == 256 and kp.wgrad_split_pixels(450, 3) == 192
+    kp.assert_fp64_parity(ref32, ref64, ref32, what="unmutated")
+    # the plain one-chain float32 sum and another split count stay inside the bar: it is not slack, nor razor thin
+    kp.assert_fp64_parity(kp.ref_conv_wgrad(*args, kp.F32, splits=1, chunk=450)["dw"], ref64, ref32, what="plain")
+    kp.assert_fp64_parity(kp.ref_conv_wgrad(*args, kp.F32, splits=3)["dw"], ref64, ref32, what="three splits")
+    with pytest.raises(AssertionError):  # creal channels read from channel 1 on
+        kp.assert_fp64_parity(kp.ref_conv_wgrad(*args, kp.F32, splits=2, c0=1)["dw"], ref64, ref32,
+                              what="channel offset")
+    with pytest.raises(AssertionError):  # the last, partial granule (pixels 448, 449) dropped
+        kp.assert_fp64_parity(kp.ref_conv_wgrad(*args, kp.F32, splits=2, drop_tail=True)["dw"], ref64, ref32,
+                              what="partial granule")
+    with pytest.raises(AssertionError):  # dw = instead of dw +=
+        kp.assert_fp64_parity(ref32 - dw0, ref64, ref32, what="dw0 dropped")
+    with pytest.raises(AssertionError):  # one split's slab left out of the fold
+        one = kp.ref_conv_wgrad(i["x"][:1], i["dy"][:1], R, R, stride, pad, 3, dw0, kp.F32, splits=1)["dw"]
+        kp.assert_fp64_parity(one, ref64, ref32, what="a slab dropped")
+
+
+def test_conv_pack_restatements():
+    w = torch.arange(2 * 3 * 2 * 2, dtype=torch.float32).reshape(2, 3, 2, 2) + 1
+    p0, p1 = kp.ref_pack_conv_weight(w, 8, 0), kp.ref_pack_conv_weight(w, 8, 1)
+    assert tuple(p0.shape) == (2, 2, 2, 8) and tuple(p1.shape) == (8, 2, 2, 2)
+    assert float(p0[1, 0, 1, 2]) == float(w[1, 2, 0, 1]) == float(p1[2, 0, 1, 1])
+    assert float(p0[..., 3:].abs().max()) == 0 and float(p1[3:].abs().max()) == 0
+    assert bool((kp.ref_pack_conv_weight(w, 8, 3) == p1).all())
+    x = torch.arange(1 * 3 * 4 * 6, dtype=torch.float32).reshape(1, 3, 4, 6)
+    xs = kp.ref_pack_input_s2d(x)
+    assert tuple(xs.shape) == (1, 5, 6, 16)
+    assert float(xs[0, 2, 2, 0]) == 0.0 and float(xs[0, 3, 4, (1 * 2 + 0) * 3 + 2]) == float(x[0, 2, 3, 4])
+    assert float(xs[..., 12:].abs().max()) == 0
+    rounds = torch.tensor([1 + 2.0 ** -8, 1 + 2.0 ** -8 + 2.0 ** -16, 1 + 3 * 2.0 ** -8]).reshape(3, 1, 1, 1)
+    assert kp.ref_pack_conv_weight(rounds, 8, 0)[:, 0, 0, 0].float().tolist() == [1.0, 1 + 2.0 ** -7, 1 + 2.0 ** -6]
